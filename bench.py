@@ -6,19 +6,21 @@ One "step" = one `train_func` call = n_disc_train (5) discriminator steps + 1 ge
 on 6 fresh synthetic batches (models/gan.py:169-173), optimizer steps included;
 images/sec = steps/s x B x n_gpus (the reference's own progress unit, train.py:298).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts its own N ranks (a child
 `torch.distributed.run`, before anything touches the GPU) and exits with the child's status.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant conv GEMM
-kernel: HIP events recorded by the library around every conv GEMM launch, on the launch stream, in
-instrumented eager steps run DIRECTLY AFTER the timed region -- hipGraph replay hides launches from
-events), `cpu_baseline` (the oracle's torch-autograd port on the host cores, bounded sample, rank 0 at
-N=1 only), at N=1 `config.secondary` (pix2pix bs 64, VAE bs 512 and the f32 headline step: SURVEY 8d
-configs 4/5 and BASELINE.md s.4's parity row) and at N>1 `collectives` (ranks seen on the RCCL group and the
-measured all-reduce time of each gradient bucket).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline
+figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last timed step when
+`--dump-outputs DIR` is given, the line.  `--full` adds the measurements that take runs of their own:
+`roofline` (dominant conv GEMM kernel: HIP events recorded by the library around every conv GEMM launch,
+on the launch stream, in instrumented eager steps run DIRECTLY AFTER the timed region -- hipGraph replay
+hides launches from events), `cpu_baseline` (the oracle's torch-autograd port on the host cores, bounded
+sample, rank 0 at N=1 only), at N=1 `config.secondary` (pix2pix bs 64, VAE bs 512 and the f32 headline
+step: SURVEY 8d configs 4/5 and BASELINE.md s.4's parity row) and at N>1 `collectives` (the measured
+all-reduce time of each gradient bucket).
 """
 import argparse
 import importlib
@@ -251,6 +253,31 @@ def roofline_of(timer, dtype, timer_steps, ms_per_step, with_traffic=True):
                            for k, v in sorted(sym.items(), key=lambda kv: -kv[1][1])}}
 
 
+DUMP_BUDGET_BYTES = 64 << 20             # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 19                 # per variable; a larger one is written as a fixed sample of this many elements
+
+
+def dump_outputs(out_dir, losses, variables, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the loss dict `train_func` returned
+    (float64 scalars) and the variables that step left (float32) -- as `out_dir/<name>.npy`, '/' in a name spelled '.'.
+    A variable larger than its share of the budget is written as the elements at a fixed sample of flat positions,
+    drawn from a generator seeded by its name and size, so that runs with the same arguments compare element for element."""
+    import re
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in losses.items()}
+    cap = min(DUMP_MAX_ELEMS, max(1, (budget - 8 * len(arrays)) // 4 // max(1, len(variables))))
+    for k, v in variables.items():
+        a = np.asarray(v, dtype=np.float32)
+        if a.size > cap:
+            rng = np.random.default_rng([zlib.crc32(k.encode()), a.size])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, cap, replace=False))]
+        arrays[k] = a
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, re.sub(r'[^A-Za-z0-9_.-]+', '.', k).strip('.') + '.npy'), a)
+    return arrays
+
+
 def time_calls(fn, warmup, steps):
     for _ in range(warmup):
         fn()
@@ -313,11 +340,16 @@ def secondary_leg(model, sess_dtype, K, rt, data, models, steps=5):
     return out
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--steps', type=int, default=10, help='timed steps (>= 1)')
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: roofline (instrumented eager steps), '
+                         'config.secondary, the CPU baselines and, at N > 1, collectives')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the losses and variables of the last step to DIR/<name>.npy')
     ap.add_argument('--batch_size', type=int, default=512)
     ap.add_argument('--latent_size', type=int, default=200)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
@@ -331,8 +363,15 @@ def main():
     ap.add_argument('--no_kernel_timer', action='store_true')
     ap.add_argument('--timer_steps', type=int, default=2)
     ap.add_argument('--no_graphs', action='store_true')
-    ap.add_argument('--dump_launches', default=None, help='diagnostics: write (kernel, GFLOP, count, avg ms, TFLOP/s) per distinct launch shape to this file')
+    ap.add_argument('--dump_launches', default=None, help='diagnostics (with --full): write (kernel, GFLOP, count, avg ms, TFLOP/s) per distinct launch shape to this file')
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rt = importlib.import_module('3dgan_amd.runtime')
     K = importlib.import_module('3dgan_amd.kernels')
@@ -376,11 +415,13 @@ def main():
         status = rep.train_func()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and sess.rank == 0:      # before anything below steps the replica again
+        dump_outputs(args.dump_outputs, status, rep.variables())
     # Per-kernel HIP events: graph replay hides the individual launches from events, so the same steps
     # are repeated eagerly, directly after the timed region, with every conv GEMM launch bracketed by events
     # on the launch stream (rank 0 only; the other ranks run the same steps so collectives stay matched).
     timer = None
-    if not args.no_kernel_timer and not args.no_headline_timer and args.timer_steps > 0:
+    if args.full and not args.no_kernel_timer and not args.no_headline_timer and args.timer_steps > 0:
         rep.use_graphs = False
         rep.train_func()
         if sess.rank == 0:
@@ -395,8 +436,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=sess.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        coll = measure_collectives(rep, sess, sync)
-        coll['ranks_seen'] = ranks_seen
+        if args.full:
+            coll = measure_collectives(rep, sess, sync)
+            coll['ranks_seen'] = ranks_seen
 
     if sess.rank == 0:
         ms = dt / args.steps * 1e3
@@ -430,7 +472,7 @@ def main():
                             % (name, gf, n, tot / n, gf / (tot / n) if tot else 0.0, tot / args.timer_steps))
         if timer:
             out['roofline'] = roofline_of(timer, args.dtype, args.timer_steps, ms)
-        if args.gpus == 1 and not args.no_secondary:
+        if args.full and args.gpus == 1 and not args.no_secondary:
             del rep
             torch.cuda.empty_cache()
             sec = {}
@@ -459,7 +501,7 @@ def main():
                 del r32
                 torch.cuda.empty_cache()
             out['config']['secondary'] = sec
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args)
         print(json.dumps(out))
     if world > 1:

@@ -337,7 +337,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(TDG_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--batch_size', '16', '--latent_size', '16', '--timer_steps', '1'],
+                        '--batch_size', '16', '--latent_size', '16', '--timer_steps', '1', '--full'],
                        env=env, timeout=900, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]

@@ -4,6 +4,6 @@
 for r in 1 2; do
 for l in "$@"; do
   echo "== $l"
-  TDG_LIB_PATH=$PWD/3dgan_amd/$l python3 bench.py --no_secondary --no_cpu_baseline --steps 20 --warmup 5 | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f ms/step' % d['ms_per_step'], {k:(v['avg_ms'],v['tflops']) for k,v in list(d['roofline']['per_kernel'].items())[:3]})"
+  TDG_LIB_PATH=$PWD/3dgan_amd/$l python3 bench.py --full --no_secondary --no_cpu_baseline --steps 20 --warmup 5 | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f ms/step' % d['ms_per_step'], {k:(v['avg_ms'],v['tflops']) for k,v in list(d['roofline']['per_kernel'].items())[:3]})"
 done
 done

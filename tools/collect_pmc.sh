@@ -12,9 +12,9 @@ WHAT=${2:-all}
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 if [ "$WHAT" = "headline" ]; then
-  CMD="python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline --no_secondary"
+  CMD="python3 bench.py --steps 3 --warmup 1 --full --no_cpu_baseline --no_secondary"
 else
-  CMD="python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline --secondary_legs pix2pix,vae"
+  CMD="python3 bench.py --steps 3 --warmup 1 --full --no_cpu_baseline --secondary_legs pix2pix,vae"
 fi
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_${TAG}_fetch -- $CMD > gpurun_out/pmc_${TAG}_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_${TAG}_write -- $CMD > gpurun_out/pmc_${TAG}_write.log 2>&1
