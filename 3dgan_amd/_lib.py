@@ -91,6 +91,13 @@ SIGNATURES = {
     'tdg_gan_logloss': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     'tdg_p2p_xent': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'tdg_p2p_l1': (_i, [_i, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_prep': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    'tdg_cgan_head_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'tdg_cgan_head_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_join': (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    'tdg_cgan_wgan_loss': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'tdg_cgan_metrics': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_metrics_workspace_bytes': (_sz, []),
     'tdg_vae_reparam': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd_kl': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp]),

@@ -7,15 +7,18 @@ def model_funcs():
     from .vae import vae
     from .cnn import cnn
 
-    def pix2pix_func(x, args, sess=None):
-        """gen-2 plugins expose .train(sess, args, feed_dict); adapt to the gen-1 train_func contract."""
-        model = get_model('pix2pix')(x, args, sess)
+    def plugin_func(name):
+        def func(x, args, sess=None):
+            """gen-2 plugins expose .train(sess, args, feed_dict); adapt to the gen-1 train_func contract."""
+            model = get_model(name)(x, args, sess)
 
-        def train_func(sess_=None, args_=None):
-            return model.train(sess_, args_, None)
-        train_func.replica = model
-        return train_func
-    return {'gan': gan, 'wgan': gan, 'iwgan': gan, 'vae': vae, 'cnn': cnn, 'pix2pix': pix2pix_func}
+            def train_func(sess_=None, args_=None):
+                return model.train(sess_, args_, None)
+            train_func.replica = model
+            return train_func
+        return func
+    return {'gan': gan, 'wgan': gan, 'iwgan': gan, 'vae': vae, 'cnn': cnn, 'pix2pix': plugin_func('pix2pix'),
+            'paper_cgan': plugin_func('paper_cgan')}
 
 
 def get_model(name):

@@ -1,0 +1,489 @@
+"""RGB-to-depth conditional GAN of the thesis experiments on MI355X -- the reference's gen-2 plugin
+`hem/models/paper_cgan.py` (arguments :14-57, __init__ :60-192, train :200-209, generators :212-310, discriminators
+:312-388, loss :390-412, metrics :447-478) on the HIP kernels.
+
+Kept: the plugin contract, the builders with the reference's variable names (`generator/encoder/vars/e1/weights`,
+`discriminator/rgb_path/vars/hx1/weights`, `discriminator/combined_path/vars/h3/bias`), xavier init of weights and biases,
+the optimizers of :64-69 (the global --optimizer / --lr do not apply), the per-version table below and the loss dict of
+`collection_to_dict(losses)`:
+
+    version          G output y_hat   D depth input real / fake   D builder
+    baseline         g                y / g                       discriminator
+    mean_adjusted    g + y_bar        y - y_bar / g               discriminator
+    mean_provided2   g + y_bar        [y - y_bar | y_bar] / [g | y_bar]   discriminator with y_bar channels
+
+The fake depth input is g itself where the reference computes (g + y_bar) - y_bar: one f32 rounding apart.
+Reference-effective behaviour and what is opt-in:
+  * `mean_provided` cannot be built by the reference (`tf.variablpe_scope`, :245): ValueError here too.
+  * wgan: the real-pass mean is named 'd_fake' a second time (:403), so TF uniquifies it: keys g_fake, d_fake, d_fake_1, d_total.
+  * wgan weight clipping (:181-187) never runs in the reference: no clip by default; with `--wgan_clip c`
+    both D and G variables are clamped to [-c, c] before their steps.
+  * the threshold metrics are tf.metrics.percentage_below: running totals since the model was built, never reset.
+
+MI355X-native: activations are NHWC; the generator's skip concats are zero-copy channel windows (as models/pix2pix.py);
+D's rgb path runs ONCE over the B images -- it is identical for D(x, y) and D(x, y_hat) -- and its output fills the left
+window of both halves of the combined input (tdg_cgan_join), its backward sums the two halves' gradients first; the depth
+path and the 1x1 combined path run as one batched pass over 2B images; the 1x1 one-channel head computes the 29x29 crop
+only (tdg_cgan_head_fwd / _bwd) and writes g straight into D's fake depth input.
+"""
+import torch
+
+from ... import _lib
+from ... import kernels as K
+from ... import engine
+from ...ops.layers import conv2d, deconv2d, concat, arg_scope, variable_scope, placeholder, reset_graph
+from ...ops.activations import Activation
+from ..._lib import ACT_LRELU, ACT_RELU
+from ...util import tower_scope_range, average_gradients, collection_to_dict
+from ..ModelPlugin import ModelPlugin
+
+VERSIONS = {'baseline': 0, 'mean_adjusted': 1, 'mean_provided2': 2}
+SRC, CROP = 65, 29
+METRIC_KEYS = ('abs_rel_diff', 'squared_rel_diff', 'linear_rmse', 'log_rmse', 'scale_invariant_log_rmse',
+               'threshold1', 'threshold2', 'threshold3')
+
+
+def _lrelu(leak):
+    return Activation('lrelu', ACT_LRELU, leak)
+
+
+_relu = Activation('relu', ACT_RELU, 0.0)
+
+
+class paper_cgan(ModelPlugin, engine.GraphRunner):
+    name = 'paper_cgan'
+
+    @staticmethod
+    def arguments():
+        """hem/models/paper_cgan.py:14-57."""
+        return {
+            '--g_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for generator.'},
+            '--d_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for discriminator.'},
+            '--g_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for generator'},
+            '--d_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for discriminator.'},
+            '--g_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for generator.'},
+            '--d_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for discriminator.'},
+            '--model_version': {'type': str, 'default': 'baseline',
+                                'choices': ['baseline', 'mean_adjusted', 'mean_provided', 'mean_provided2'],
+                                'help': 'Which version of the model to run.'},
+            '--training_version': {'type': str, 'default': 'gan', 'choices': ['gan', 'wgan'],
+                                   'help': 'Whether to use standard GAN training of Wasserstein GAN training.'},
+        }
+
+    # ------------------------------------------------------------------------------ builders
+    @staticmethod
+    def check_version(version):
+        if version == 'mean_provided':
+            raise ValueError("paper_cgan --model_version mean_provided cannot be built: the reference's g_mean_provided "
+                             "calls tf.variablpe_scope (hem/models/paper_cgan.py:245) and raises AttributeError")
+        if version not in VERSIONS:
+            raise ValueError('paper_cgan: unknown --model_version %r' % version)
+
+    @staticmethod
+    def generator(x, args, reuse=False):
+        """g_baseline (:212-243) and g_mean_provided2 (:277-310): x [B,65,65,3|4] -> the 31x31x1 head, cropped to 29x29
+        by the executor.  Returns (d4 output, the records of the decoder concats)."""
+        B = args.batch_size
+        with variable_scope('encoder'), arg_scope([conv2d], reuse=reuse, filter_size=5, stride=2, padding='VALID', init='xavier',
+                                                  activation=_relu):
+            e1 = conv2d(x, x.shape[-1], 64, name='e1')          # 31x31x64
+            e2 = conv2d(e1, 64, 128, name='e2')                 # 14x14x128
+            e3 = conv2d(e2, 128, 256, name='e3')                # 5x5x256
+            e4 = conv2d(e3, 256, 512, name='e4')                # 1x1x512
+        with variable_scope('decoder'), arg_scope([deconv2d, conv2d], reuse=reuse, filter_size=5, stride=2, init='xavier',
+                                                  padding='VALID', activation=_lrelu(0.2)):
+            y = deconv2d(e4, 512, 256, output_shape=(B, 256, 5, 5), name='d1')
+            c1 = y = concat([y, e3])                           # 5x5x512
+            y = deconv2d(y, 512, 128, output_shape=(B, 128, 14, 14), name='d2')
+            c2 = y = concat([y, e2])                           # 14x14x256
+            y = deconv2d(y, 256, 64, output_shape=(B, 64, 31, 31), name='d3')
+            c3 = y = concat([y, e1])                           # 31x31x128
+            y = conv2d(y, 128, 1, stride=1, filter_size=1, padding='SAME', activation=None, name='d4')   # 31x31x1
+        return y, (c1, c2, c3)
+
+    @staticmethod
+    def discriminator(x, y, args, reuse=False):
+        """d_baseline (:312-338) / d_mean_provided2 (:362-388, x and y already carry their y_bar channel).
+        Returns the logits [B,1,1,1] and the two path outputs."""
+        with arg_scope([conv2d], reuse=reuse, activation=_lrelu(0.2), init='xavier', padding='VALID', filter_size=5, stride=2):
+            with variable_scope('rgb_path'):
+                h1 = conv2d(x, x.shape[-1], 64, name='hx1')     # 31x31x64
+                h1 = conv2d(h1, 64, 128, name='hx2')            # 14x14x128
+                h1 = conv2d(h1, 128, 256, name='hx3')           # 5x5x256
+                h1 = conv2d(h1, 256, 512, name='hx4')           # 1x1x512
+            with variable_scope('depth_path'):
+                h2 = conv2d(y, y.shape[-1], 128, name='hy1')    # 13x13x128 (the reference's "14x14" comment at :326 is off)
+                h2 = conv2d(h2, 128, 256, name='hy2')           # 5x5x256
+                h2 = conv2d(h2, 256, 512, name='hy3')           # 1x1x512
+            with variable_scope('combined_path'):
+                h = concat([h1, h2])                            # 1x1x1024
+                h = conv2d(h, 1024, 1024, stride=1, filter_size=1, padding='SAME', name='h1')
+                h = conv2d(h, 1024, 512, stride=1, filter_size=1, padding='SAME', name='h2')
+                h = conv2d(h, 512, 1, stride=1, filter_size=1, padding='SAME', name='h3', activation=None)
+        return h, h1, h2
+
+    @staticmethod
+    def build_graph(args):
+        """Record both networks for `args` (no device work); returns the Nets by scope name."""
+        paper_cgan.check_version(args.model_version)
+        mp2 = args.model_version == 'mean_provided2'
+        reset_graph()
+        xs = placeholder((None, SRC, SRC, 3))
+        gx = concat([xs, placeholder((None, SRC, SRC, 1), 'ones')]) if mp2 else xs
+        rx = concat([xs, placeholder((None, SRC, SRC, 1), 'y_bar')]) if mp2 else xs
+        dy = placeholder((None, CROP, CROP, 2 if mp2 else 1), 'y')
+        with variable_scope('generator'):
+            paper_cgan.generator(gx, args)
+        with variable_scope('discriminator'):
+            paper_cgan.discriminator(rx, dy, args, reuse=False)      # D(x, y_hat) first, as :123-136
+            paper_cgan.discriminator(rx, dy, args, reuse=True)
+        from ...ops import layers as Lyr
+        return {k: v for k, v in Lyr._nets.items() if v.passes}
+
+    # ------------------------------------------------------------------------------ construction
+    S_GFAKE, S_DFAKE, S_DREAL, S_DTOTAL = 0, 1, 2, 3
+
+    def __init__(self, x_y, args, sess=None):
+        from ...runtime import Session
+        self.args, self.x_y = args, x_y
+        self.sess = sess = sess or Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
+        for flag, default in paper_cgan._defaults().items():
+            if not hasattr(args, flag):
+                setattr(args, flag, default)
+        self.check_version(args.model_version)
+        self.version = VERSIONS[args.model_version]
+        self.wgan = args.training_version == 'wgan'
+        B = self.B = args.batch_size
+        dev, dt = sess.device, sess.dtype
+        for _ in tower_scope_range(None, args.n_gpus, B, sess):
+            nets = self.build_graph(args)
+        self.enet, self.dec_net = nets['generator/encoder'], nets['generator/decoder']
+        rgb_net, depth_net, comb_net = (nets['discriminator/' + s] for s in ('rgb_path', 'depth_path', 'combined_path'))
+
+        self.ws = K.Workspace(dev)
+        self.g_store, self.d_store = engine.ParamStore(dev), engine.ParamStore(dev)
+        mp2 = self.version == 2
+        # D: combined path over 2B (images [0,B) real, [B,2B) fake), depth path over 2B, rgb path over B
+        self.Dc = engine.SeqNet(comb_net, 2 * B, (1, 1, 1024), dt, dev, self.d_store, need_input_grad=True, ws=self.ws)
+        self.Dr = engine.SeqNet(rgb_net, B, (SRC, SRC, 4 if mp2 else 3), dt, dev, self.d_store, ws=self.ws)
+        self.Dd = engine.SeqNet(depth_net, 2 * B, (CROP, CROP, 2 if mp2 else 1), dt, dev, self.d_store, need_input_grad=True,
+                                ws=self.ws)
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.declare_variables()
+        self.rgb_g = self.Dr.layers[-1].gout                 # dL/d(rgb path output): both halves summed by tdg_cgan_join
+        self.depth_g = self.Dd.layers[-1].gout
+        # G input: D's rgb input where the two are the same tensor (baseline, mean_adjusted)
+        self.gx = K.Act(B, SRC, SRC, 4, dt, dev) if mp2 else self.Dr.x
+        self.G = CganGenerator(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx,
+                               fake=self.Dd.x.view(B, B), dfake=self.Dd.dx.view(B, B))
+        self.d_store.allocate()
+        self.g_store.allocate()
+        gen = torch.Generator().manual_seed(sess.seed)
+        self.G.init_variables(gen)
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.init_variables(gen)
+        if self.wgan:                                        # :64-66
+            self.g_opt = engine.RMSProp(self.g_store, args.g_lr, decay=0.9, momentum=0.0, eps=1e-10)
+            self.d_opt = engine.Adam(self.d_store, args.d_lr)
+        else:                                                # :67-69
+            self.g_opt = engine.Adam(self.g_store, args.g_lr, args.g_beta1, args.g_beta2)
+            self.d_opt = engine.Adam(self.d_store, args.d_lr, args.d_beta1, args.d_beta2)
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        self.x_stage, self.y_stage = f32(B, SRC, SRC, 3), f32(B, SRC, SRC, 1)
+        self.ybar, self.crop, self.yhat = f32(B), f32(B, CROP, CROP), f32(B, CROP, CROP)     # of the last loss fetch
+        self.inf_ybar, self.inf_crop, self.inf_yhat = f32(B), f32(B, CROP, CROP), f32(B, CROP, CROP)   # infer()'s own
+        self.scal = f32(8)
+        # streaming threshold totals of tf.metrics.percentage_below, one per metric set: hits 1..3, elements
+        self.counts = {k: torch.zeros(4, dtype=torch.int64, device=dev) for k in ('y_hat', 'y_0')}
+        self.metric_out = f32(8)
+        self.metric_ws = torch.zeros(_lib.load().tdg_cgan_metrics_workspace_bytes(), dtype=torch.uint8, device=dev)
+        self.init_graphs(args, sess)
+        self.refresh()
+
+    @staticmethod
+    def _defaults():
+        return {k.lstrip('-'): v['default'] for k, v in paper_cgan.arguments().items()}
+
+    # ---- variables -----------------------------------------------------------------------------------
+    def stores(self):
+        return [self.g_store, self.d_store]
+
+    def optimizers(self):
+        return {'optimizers/generator': self.g_opt, 'optimizers/discriminator': self.d_opt}
+
+    def refresh(self):
+        self.G.repack()
+        self._repack_d()
+
+    def _repack_d(self):
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.repack()
+
+    def load_variables(self, arrays):
+        self.g_store.load(arrays)
+        self.d_store.load(arrays)
+        self.refresh()
+
+    def variables(self):
+        d = self.g_store.state_dict()
+        d.update(self.d_store.state_dict())
+        return d
+
+    def gradients(self):
+        d = self.g_store.grads_dict()
+        d.update(self.d_store.grads_dict())
+        return d
+
+    # ---- pieces ------------------------------------------------------------------------------------------
+    def _stage(self, batch):
+        """The batch at fixed device addresses (the step bodies are graph-captured)."""
+        x01, y01 = batch
+        self.x_stage.copy_(x01.reshape(self.x_stage.shape))
+        self.y_stage.copy_(y01.reshape(self.y_stage.shape))
+
+    def _inputs(self, ybar, crop):
+        """x into G's (and D's rgb) input, the depth target and the constant channels (:83-96, :286, :323, :326);
+        y_bar and the f32 crop into `ybar` / `crop`."""
+        B, dt = self.B, self.sess.dtype
+        rows = B * SRC * SRC
+        _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.Dr.x.cs, 1.0, 0.0, self.Dr.x.ptr(0), K.stream())
+        mp2 = self.version == 2
+        if mp2:
+            _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.gx.cs, 1.0, 0.0, self.gx.ptr(0), K.stream())
+        _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage), B, self.version, self.Dd.x.ptr(0), self.Dd.x.cs,
+                  self.Dd.x.ptr(B) if mp2 else None, K.ptr(ybar), K.ptr(crop),
+                  self.gx.window(3, 1).ptr(0) if mp2 else None, self.gx.cs,
+                  self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs, K.stream())
+
+    def _generate(self, ybar, yhat):
+        """g into D's fake depth input, y_hat = g (+ y_bar, :113-121) into `yhat`."""
+        self.G.forward(ybar if self.version != 0 else None, yhat)
+
+    def _d_forward(self):
+        B, dt = self.B, self.sess.dtype
+        self.Dr.forward(0, B)
+        self.Dd.forward(0, 2 * B)
+        rh, dh = self.Dr.layers[-1].h, self.Dd.layers[-1].h
+        _lib.call('tdg_cgan_join', dt, 0, B, 2 * B, 512, self.Dc.x.ptr(0), self.Dc.x.cs, rh.ptr(0), rh.cs, dh.ptr(0), dh.cs, K.stream())
+        self.Dc.forward(0, 2 * B)
+
+    def _loss(self, mode):
+        last = self.Dc.layers[-1]
+        if self.wgan:
+            _lib.call('tdg_cgan_wgan_loss', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
+                      K.ptr(self.scal), K.stream())
+        else:        # tdg_p2p_xent writes d_real, d_fake, g_fake to scal[0..2] of the pointer, here self.scal[4..6] (_losses)
+            _lib.call('tdg_p2p_xent', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
+                      K.ptr(self.scal, 16), K.stream())
+
+    def _clip(self, store, repack):
+        """--wgan_clip c (opt-in; :181-187 never runs in the reference): clamp before the step."""
+        c = float(getattr(self.args, 'wgan_clip', 0.0) or 0.0)
+        if self.wgan and c > 0.0:
+            _lib.call('tdg_clamp', K.ptr(store.params), store.size, -c, c, K.stream())
+            repack()
+
+    # ---- steps ---------------------------------------------------------------------------------------------
+    def d_step(self, batch):
+        self._stage(batch)
+        self._run('d_grads', self._d_grads)
+        self.sess.assert_finite(self.d_store, 'd_step')
+        self._scale = average_gradients(self.sess, self.d_store)      # RCCL, outside the graphs
+        self._run('d_apply', self._d_apply)
+        self.sess.global_step += 1
+
+    def _d_grads(self):
+        B, dt = self.B, self.sess.dtype
+        self._clip(self.d_store, self._repack_d)
+        self._inputs(self.ybar, self.crop)
+        self._generate(self.ybar, self.yhat)
+        self._d_forward()
+        self._loss(1)
+        self.Dc.backward(0, 2 * B, want_params=True, want_dx=True)
+        dx = self.Dc.dx
+        _lib.call('tdg_cgan_join', dt, 1, B, 2 * B, 512, dx.ptr(0), dx.cs, self.rgb_g.ptr(0), self.rgb_g.cs, self.depth_g.ptr(0),
+                  self.depth_g.cs, K.stream())
+        self.Dd.backward(0, 2 * B, want_params=True)
+        self.Dr.backward(0, B, want_params=True)
+
+    def _d_apply(self):
+        self.d_opt.step(self._scale)
+        self._repack_d()
+
+    def g_step(self, batch):
+        self._stage(batch)
+        self._run('g_grads', self._g_grads)
+        self.sess.assert_finite(self.g_store, 'g_step')
+        self._scale = average_gradients(self.sess, self.g_store)
+        self._run('g_apply', self._g_apply)
+        self.sess.global_step += 1
+
+    def _g_grads(self):
+        """The G step and the loss fetch of one sess.run (:208): D runs on both halves, the losses are this batch's."""
+        B, dt = self.B, self.sess.dtype
+        self._clip(self.g_store, self.G.repack)
+        self._inputs(self.ybar, self.crop)
+        self._generate(self.ybar, self.yhat)
+        self._d_forward()
+        self._loss(2)
+        self.Dc.backward(B, B, want_params=False, want_dx=True)
+        dx = self.Dc.dx
+        _lib.call('tdg_cgan_join', dt, 1, B, B, 512, dx.ptr(B), dx.cs, None, 0, self.depth_g.ptr(B), self.depth_g.cs, K.stream())
+        self.Dd.backward(B, B, want_params=False, want_dx=True)
+        self.G.backward()
+
+    def _g_apply(self):
+        self.g_opt.step(self._scale)
+        self.G.repack()
+
+    def _losses(self):
+        s = self.sess.report_scalars(self.scal, mean=getattr(self.args, 'mean_loss', False)).cpu().tolist()
+        r = self.sess.world_size - 1
+        if self.wgan:                    # :396-403: the real mean is named 'd_fake' again -> 'd_fake_1'
+            items = [('loss/generator/g_fake', s[0]), ('loss/discriminator/d_fake', s[1]), ('loss/discriminator/d_fake_1', s[2]),
+                     ('loss/discriminator/d_total', s[3])]
+        else:                            # :398-407 (scal[4..6] = d_real, d_fake, g_fake of tdg_p2p_xent)
+            items = [('loss/generator/g_fake', s[6]), ('loss/discriminator/d_fake', s[5]), ('loss/discriminator/d_real', s[4]),
+                     ('loss/discriminator/d_total', s[4] + s[5])]
+        return collection_to_dict([('tower_%d/%s:0' % (r, n), v) for n, v in items])
+
+    def train(self, sess=None, args=None, feed_dict=None):
+        """:200-209: gan -- one D step, then the G step and the loss fetch on the next batch; wgan -- five D steps first."""
+        for _ in range(5 if self.wgan else 1):
+            self.d_step(self.x_y.next_batch())
+        self.g_step(self.x_y.next_batch())
+        return self._losses()
+
+    # ---- evaluation ----------------------------------------------------------------------------------------
+    def metrics(self):
+        """The Eigen-2014 sets `metrics_y_hat` and `metrics_y_0` (:171-172, :447-478) of the last loss fetch's batch.
+        Each call is one evaluation of the streaming threshold metrics."""
+        out = {}
+        y_0 = self.ybar if self.version != 0 else None          # y_0 = 0 (baseline) or y_bar
+        for name, pred, off in (('y_hat', self.yhat, None), ('y_0', None, y_0)):
+            _lib.call('tdg_cgan_metrics', K.ptr(self.crop), K.ptr(pred), K.ptr(off), self.B, CROP * CROP, K.ptr(self.counts[name]),
+                      K.ptr(self.metric_out), K.ptr(self.metric_ws), self.metric_ws.numel(), K.stream())
+            out['metrics_' + name] = dict(zip(METRIC_KEYS, self.metric_out.cpu().tolist()))
+        return out
+
+    def infer(self, batch):
+        """y_hat [B,29,29,1] f32 of one (x, y) batch (y supplies y_bar for the mean-adjusted versions).  It has buffers of its
+        own: metrics() keeps reporting the last loss fetch."""
+        self._stage(batch)
+        self._inputs(self.inf_ybar, self.inf_crop)
+        self._generate(self.inf_ybar, self.inf_yhat)
+        return self.inf_yhat.reshape(self.B, CROP, CROP, 1).clone()
+
+
+# ------------------------------------------------------------------------------------------------------
+class CganGenerator:
+    """The 4-down / 3-up generator with zero-copy skip concats and the cropped 1x1 head.
+
+    cat[1] = [d1 | e3] (5x5x512), cat[2] = [d2 | e2] (14x14x256), cat[3] = [d3 | e1] (31x31x128); gcat[i] their gradients.
+    Encoder layer k (k <= 3) writes its activation into the right window of cat[4-k] and receives its gradient -- skip path
+    first, main path accumulated on top -- in the right window of gcat[4-k], as models/pix2pix.py's UNet.
+    """
+
+    def __init__(self, enet, dnet, B, dtype, device, store, ws, x_in, fake, dfake):
+        self.B, self.dtype, self.store, self.ws = B, dtype, store, ws
+        self.enet, self.dnet = enet, dnet
+        E, Dc = enet.layers, dnet.layers
+        assert len(E) == 4 and len(Dc) == 4
+        A = lambda h, w, c: K.Act(B, h, w, c, dtype, device)
+        self.x_in, self.fake, self.dfake = x_in, fake, dfake
+        sizes = [E[k].out_shape for k in range(4)]                 # (31,31,64) (14,14,128) (5,5,256) (1,1,512)
+        self.cat, self.gcat = {}, {}
+        for i in range(1, 4):
+            cd, ce = Dc[i - 1].out_size, E[3 - i].out_size
+            h, w, _ = sizes[3 - i]
+            if Dc[i].in_size != cd + ce:
+                raise ValueError('decoder layer %d expects %d input channels, skip concat provides %d' % (i + 1, Dc[i].in_size, cd + ce))
+            self.cat[i], self.gcat[i] = A(h, w, cd + ce), A(h, w, cd + ce)
+        self.e_h, self.e_g = {}, {}
+        for k in range(1, 5):
+            co = E[k - 1].out_size
+            if k <= 3:
+                cd = Dc[3 - k].out_size
+                self.e_h[k], self.e_g[k] = self.cat[4 - k].window(cd, co), self.gcat[4 - k].window(cd, co)
+            else:
+                self.e_h[k], self.e_g[k] = A(1, 1, co), A(1, 1, co)
+        self.d_h = {i: self.cat[i].window(0, Dc[i - 1].out_size) for i in range(1, 4)}
+        self.d_g = {i: self.gcat[i].window(0, Dc[i - 1].out_size) for i in range(1, 4)}
+        self.head = Dc[3]
+        if (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.cat[3].c):
+            raise ValueError('the generator head must be a 1x1 conv from the last concat to one channel')
+        self.e_conv = {k: K.Conv(self.x_in if k == 1 else self.e_h[k - 1], self.e_h[k], 5, 5, 2, 0, 0) for k in range(1, 5)}
+        self.d_conv = {i: K.Conv(self.d_h[i], self.e_h[4] if i == 1 else self.cat[i - 1], 5, 5, 2, 0, 0) for i in range(1, 4)}
+        for net in (enet, dnet):
+            for l in net.layers:
+                store.declare(net.var_name(l, 'weights'), l.filter_shape)
+                store.declare(net.var_name(l, 'bias'), (l.out_size,))
+        self._pack_jobs = None
+        self.head_ws = torch.zeros(B * (self.cat[3].c + 1), dtype=torch.float32, device=device)
+
+    def init_variables(self, gen):
+        for net in (self.enet, self.dnet):
+            for l in net.layers:
+                for which, shape in (('weights', l.filter_shape), ('bias', (l.out_size,))):
+                    cpu = torch.empty(shape, dtype=torch.float32)
+                    engine.xavier_uniform_(cpu, shape, gen)
+                    self.store[net.var_name(l, which)].copy_(cpu)
+
+    def repack(self):
+        if self._pack_jobs is None:
+            jl = [self.e_conv[k].pack_job(self.store[self.enet.var_name(self.enet.layers[k - 1], 'weights')]) for k in range(1, 5)]
+            jl += [self.d_conv[i].pack_job(self.store[self.dnet.var_name(self.dnet.layers[i - 1], 'weights')]) for i in range(1, 4)]
+            self._pack_jobs = K.make_pack_jobs(jl)
+        K.pack_all(self._pack_jobs)
+
+    def _var(self, net, l, which):
+        return self.store[net.var_name(l, which)]
+
+    def forward(self, ybar, yhat):
+        """g into channel 0 of D's fake depth input, y_hat = g (+ y_bar when given) into `yhat` (f32)."""
+        B = self.B
+        E, Dc = self.enet.layers, self.dnet.layers
+        for k in range(1, 5):
+            spec = E[k - 1]
+            src = self.x_in if k == 1 else self.e_h[k - 1]
+            self.e_conv[k].fwd(src.ptr(), self.e_h[k].ptr(), B,
+                               K.epilogue(bias=self._var(self.enet, spec, 'bias'), act=spec.act.code, leak=spec.act.leak))
+        for i in range(1, 4):
+            spec = Dc[i - 1]
+            src = self.e_h[4] if i == 1 else self.cat[i - 1]
+            self.d_conv[i].bwd_data(src.ptr(), self.d_h[i].ptr(), B,
+                                    K.epilogue(bias=self._var(self.dnet, spec, 'bias'), act=spec.act.code, leak=spec.act.leak))
+        c3 = self.cat[3]
+        _lib.call('tdg_cgan_head_fwd', self.dtype, c3.ptr(), B, c3.h, c3.c, c3.cs, CROP, K.ptr(self._var(self.dnet, self.head, 'weights')),
+                  K.ptr(self._var(self.dnet, self.head, 'bias')), K.ptr(ybar), K.ptr(yhat), self.fake.ptr(0), self.fake.cs, K.stream())
+
+    def backward(self):
+        """From dL/dg in channel 0 of D's fake depth-input gradient."""
+        B, st, g = self.B, self.store, self.store.grad
+        E, Dc = self.enet.layers, self.dnet.layers
+        c3, gc3 = self.cat[3], self.gcat[3]
+        _lib.call('tdg_cgan_head_bwd', self.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), B, c3.h, c3.c, c3.cs, CROP,
+                  K.ptr(st[self.dnet.var_name(self.head, 'weights')]), K.MASK_LRELU, Dc[2].act.leak, gc3.ptr(),
+                  K.ptr(g(self.dnet.var_name(self.head, 'weights'))), K.ptr(g(self.dnet.var_name(self.head, 'bias'))),
+                  K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
+        # gcat[i] now holds [delta of d_i | dL/de_{4-i} from the skip] (the lrelu mask of d_i applied by its producer)
+        for i in range(3, 0, -1):
+            spec, conv = Dc[i - 1], self.d_conv[i]
+            delta = self.d_g[i]
+            K.bias_grad(self.ws, delta, spec.out_size, g(self.dnet.var_name(spec, 'bias')))
+            src = self.e_h[4] if i == 1 else self.cat[i - 1]
+            conv.bwd_filter(delta.ptr(), src.ptr(), g(self.dnet.var_name(spec, 'weights')), B, 0.0)
+            if i > 1:      # first writer of gcat[i-1], both windows; lrelu'(cat) is exact on d's window, 1 on e's where e > 0
+                conv.fwd(delta.ptr(), self.gcat[i - 1].ptr(), B,
+                         K.epilogue(mask_mode=K.MASK_LRELU, leak=Dc[i - 2].act.leak, mask_src=self.cat[i - 1].ptr()))
+            else:
+                conv.fwd(delta.ptr(), self.e_g[4].ptr(), B, K.epilogue(mask_mode=K.MASK_RELU, mask_src=self.e_h[4].ptr()))
+        for k in range(4, 0, -1):
+            spec, conv = E[k - 1], self.e_conv[k]
+            delta = self.e_g[k]
+            K.bias_grad(self.ws, delta, spec.out_size, g(self.enet.var_name(spec, 'bias')))
+            src = self.x_in if k == 1 else self.e_h[k - 1]
+            conv.bwd_filter(src.ptr(), delta.ptr(), g(self.enet.var_name(spec, 'weights')), B, 0.0)
+            if k > 1:      # + the main path on top of the skip gradient, then relu'(e_{k-1})
+                conv.bwd_data(delta.ptr(), self.e_g[k - 1].ptr(), B,
+                              K.epilogue(mask_mode=K.MASK_RELU, mask_src=self.e_h[k - 1].ptr(), accumulate=True))

@@ -28,13 +28,25 @@ def model_plugins():
     return search_for_plugins(os.path.join(_HERE, 'models'), '3dgan_amd.models', 'ModelPlugin')
 
 
+def paper_model_plugins():
+    """The thesis experiments (hem/models/paper_*.py) have a plugin directory of their own, `3dgan_amd/models/paper/`."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'paper'), '3dgan_amd.models.paper', 'ModelPlugin')
+
+
+def all_model_plugins():
+    """Every `--model` plugin: both directories."""
+    found = model_plugins()
+    found.update(paper_model_plugins())
+    return found
+
+
 def data_plugins():
     return search_for_plugins(os.path.join(_HERE, 'data_plugins'), '3dgan_amd.data_plugins', 'DataPlugin')
 
 
 def get_model(name):
     """hem/models/ModelPlugin.py:4-8: the plugin class registered under `name` (KeyError for an unknown name, as there)."""
-    return model_plugins()[name]
+    return all_model_plugins()[name]
 
 
 def get_dataset(name):

@@ -267,6 +267,54 @@ int tdg_p2p_xent(int dtype, const void* logits, int rows, int cs, int mode, void
  * hem/ops/losses.py:10-11) after rescaling both to [0,1].  If dg != NULL: dg[r*dgs] += weight * d l1 / d g. */
 int tdg_p2p_l1(int dtype, const void* y, const void* g, int rows, int cs, float weight, void* dg, int dgs, float* scal,
                void* workspace, size_t workspace_bytes, void* stream);
+/* ---- paper_cgan pieces (hem/models/paper_cgan.py; 3dgan_amd/csrc/tdg_cgan.hip) ------------------------------------
+ * tdg_cgan_prep: one workgroup per image of the staged f32 depth y [n,65,65] (:90-96):
+ *   crop[b] = 10 * y[b, 17:46, 17:46] (f32 [n,29,29]), ybar[b] = mean(crop[b]) (f32 [n]);
+ *   depth_real (channel 0 of the real half of D's depth input [n,29,29,depth_cs]) = crop (version 0, baseline) or
+ *   crop - ybar (1, mean_adjusted; 2, mean_provided2).  Version 2 also writes channel 1 = ybar of depth_real AND of
+ *   depth_fake (the fake half, same layout).  g_ones (nullable): that channel of [n,65,65,g_cs] = 1 (mean_provided2's G
+ *   input, :286); rgb_ybar (nullable): that channel of [n,65,65,rgb_cs] = ybar (mean_provided2's rgb D input, :323). */
+int tdg_cgan_prep(int dtype, const float* y, int n, int version, void* depth_real, int depth_cs, void* depth_fake, float* ybar,
+                  float* crop, void* g_ones, int g_cs, void* rgb_ybar, int rgb_cs, void* stream);
+/* tdg_cgan_head_fwd: the generator head d4 (1x1 conv, cin -> 1, no activation) on the top-left crop x crop pixels of the
+ * hw x hw concat [n,hw,hw,cs] only (:241-242): g = w . cat + b.  yhat = g + ybar[b] (ybar nullable: + 0), f32 [n,crop,crop];
+ * fake (channel 0 of D's fake depth input, channel stride fake_cs, compute dtype) = g.  cin in {64,128,256,512}. */
+int tdg_cgan_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w, const float* b,
+                      const float* ybar, float* yhat, void* fake, int fake_cs, void* stream);
+/* tdg_cgan_head_bwd: from delta = dL/dg (channel 0 of dfake, [n,crop,crop,fake_cs]):
+ *   dcat[p, c] = delta[p] * w[c] * mask(cat[p, c]) inside the crop, 0 outside it (the first writer of dcat);
+ *   dw[c] = sum_p delta[p] * cat[p, c], db[0] = sum_p delta[p]  (f32, overwritten; per-image partials in the workspace of
+ *   n * (cin + 1) floats, summed in image order: deterministic).  mask_mode / leak as in TdgEpilogue (TDG_MASK_LRELU: the
+ *   derivative of the decoder's lrelu on its window; on the relu encoder window it is replaced by the relu mask the
+ *   encoder's backward-data epilogue applies after adding the main path). */
+int tdg_cgan_head_bwd(int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs, int crop,
+                      const float* w, int mask_mode, float leak, void* dcat, float* dw, float* db, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* tdg_cgan_join: D's combined input [rows, comb_cs] = [rgb path output | depth path output] (:332) where the rgb path ran
+ * ONCE over n_rgb images (it is the same for D(x,y) and D(x,yhat)) and the depth path over both halves.
+ *   mode 0: comb[r, 0:c] = rgb[r % n_rgb], comb[r, c:2c] = depth[r]                                   (r < rows)
+ *   mode 1: depth[r] = comb[r, c:2c]; if rgb: rgb[b] = comb[b, 0:c] + comb[n_rgb + b, 0:c]   (b < n_rgb, rows >= 2 n_rgb)
+ * c, the strides and the pointers are multiples of 8 elements (16-byte vector access). */
+int tdg_cgan_join(int dtype, int mode, int n_rgb, int rows, int c, void* comb, int comb_cs, void* rgb, int rgb_cs, void* depth,
+                  int depth_cs, void* stream);
+/* tdg_cgan_wgan_loss: WGAN losses on the SIGMOID outputs (:395-403) of the 1x1 logits (channel 0, row stride cs) of the
+ * real pass (rows [0, rows)) and the fake pass (rows [rows, 2*rows)):
+ *   scal[0] = g_fake = -mean s(z_fake), scal[1] = d_fake = mean s(z_fake), scal[2] = d_real = mean s(z_real),
+ *   scal[3] = d_total = d_fake - d_real.
+ * mode 1 (D step): seed_real = -s(1-s)/rows, seed_fake = +s(1-s)/rows; mode 2 (G step): seed_fake = -s(1-s)/rows,
+ * seed_real = 0; mode 0: losses only.  seed has the layout of logits. */
+int tdg_cgan_wgan_loss(int dtype, const void* logits, int rows, int cs, int mode, void* seed, float* scal, void* stream);
+/* tdg_cgan_metrics: the Eigen-2014 metrics of one set (:447-478) on a = y / 10, p = pred / 10 over n images of hw pixels:
+ * y f32 [n*hw] (10x depth), pred = pred[i] (nullable: 0) + offset[i / hw] (nullable: 0).
+ *   out[0] abs_rel_diff = mean(|a-p|/p), out[1] squared_rel_diff = mean((a-p)^2/p), out[2] linear_rmse,
+ *   out[3] log_rmse, out[4] scale_invariant_log_rmse = mean(d^2) - (sum d)^2/n^2  (d = log(a+1e-8) - log(p+1e-8)),
+ *   out[5..7] threshold1..3: tf.metrics.percentage_below(max(a/p, p/a), 1.25^k) -- STREAMING: counts[0..2] (hits) and
+ *   counts[3] (elements) are device-resident running totals, never reset, and out = counts[k] / counts[3].
+ * Division by a non-positive p gives inf / NaN exactly where the formulas do.  Per-block f64 partials in the workspace
+ * (tdg_cgan_metrics_workspace_bytes()), finished in block order by a second launch: deterministic. */
+int tdg_cgan_metrics(const float* y, const float* pred, const float* offset, int n, int hw, unsigned long long* counts, float* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t tdg_cgan_metrics_workspace_bytes(void);
 /* ---- VAE pieces (models/vae.py:66-90,113-129) -------------------------------------------------------
  * heads = [z_mean | z_stddev] rows of 2L (channel stride hs); z = mean + stddev * eps (models/vae.py:128) */
 int tdg_vae_reparam(int dtype, const void* heads, int hs, const void* eps, int es, int rows, int L, void* z, int zs,
