@@ -98,6 +98,10 @@ SIGNATURES = {
     'tdg_cgan_wgan_loss': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'tdg_cgan_metrics': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_metrics_workspace_bytes': (_sz, []),
+    'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
+    'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'tdg_cgan_full_rmse': (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     'tdg_vae_reparam': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd_kl': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp]),

@@ -39,6 +39,9 @@ from ..ModelPlugin import ModelPlugin
 
 VERSIONS = {'baseline': 0, 'mean_adjusted': 1, 'mean_provided2': 2}
 SRC, CROP = 65, 29
+FULL_OFFSET = 18                 # paper_fullimage.py:138 places the 29x29 output at +18 (training crops the target at +17)
+FULL_MIN_SIDE = SRC + CROP       # 94: the smallest frame side with one window
+FULL_RMSE_BLOCKS = 256           # tdg_cgan_full_rmse's workspace, in doubles
 METRIC_KEYS = ('abs_rel_diff', 'squared_rel_diff', 'linear_rmse', 'log_rmse', 'scale_invariant_log_rmse',
                'threshold1', 'threshold2', 'threshold3')
 
@@ -197,6 +200,7 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         self.counts = {k: torch.zeros(4, dtype=torch.int64, device=dev) for k in ('y_hat', 'y_0')}
         self.metric_out = f32(8)
         self.metric_ws = torch.zeros(_lib.load().tdg_cgan_metrics_workspace_bytes(), dtype=torch.uint8, device=dev)
+        self._full = {}                                      # infer_full's frame buffers by (H, W, stride)
         self.init_graphs(args, sess)
         self.refresh()
 
@@ -373,6 +377,117 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         self._inputs(self.inf_ybar, self.inf_crop)
         self._generate(self.inf_ybar, self.inf_yhat)
         return self.inf_yhat.reshape(self.B, CROP, CROP, 1).clone()
+
+    # ---- full-frame inference (paper_fullimage.py) -----------------------------------------------------------
+    def infer_full(self, image, depth, stride=10, offset=FULL_OFFSET):
+        """The 65x65 window slid over a whole frame at `stride` (build_batch / reconstruct / rmse of paper_fullimage.py:90-163).
+
+        image f32 [H,W,3] and depth f32 [H,W] or [H,W,1] in [0, 1] (torch or NumPy).  Every window runs through infer()'s
+        path (depth feeds y_bar only) in chunks of batch_size, one graph-replayed body per chunk; the 29x29 outputs are
+        blended into frame canvases at +offset, in the reference's order.  Returns a FullFrame: y_hat and g canvases
+        (device f32 [H,W]), the frame RMSE, the patch count and the grid (cols, rows)."""
+        image, depth = self._frame(image, depth)
+        H, W = int(image.shape[0]), int(image.shape[1])
+        grid = patch_grid(H, W, stride)
+        if grid.patches == 0:
+            raise ValueError('infer_full: no %dx%d window fits a %dx%d frame at stride %d' % (SRC, SRC, H, W, stride))
+        if not 0 <= offset <= SRC - CROP:
+            raise ValueError('infer_full: offset %d outside [0, %d]' % (offset, SRC - CROP))
+        fb = self._full_buffers(H, W, stride, grid)
+        fb.image.copy_(image)
+        fb.depth.copy_(depth)
+        fb.chunk.zero_()
+        name = 'full_%d_%d_%d' % (H, W, stride)
+        for _ in range(fb.n_chunks):
+            self._run(name, lambda: self._full_chunk(fb, H, W, stride))
+        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), fb.slots, H, W, stride, offset,
+                  K.ptr(fb.yhat), K.ptr(fb.g), K.stream())
+        _lib.call('tdg_cgan_full_rmse', K.ptr(fb.depth), K.ptr(fb.yhat), H, W, K.ptr(fb.rmse), K.ptr(fb.rmse_ws),
+                  fb.rmse_ws.numel() * 8, K.stream())
+        return FullFrame(fb.yhat.clone(), fb.g.clone(), float(fb.rmse.item()), grid.patches, (grid.cols, grid.rows))
+
+    def _frame(self, image, depth):
+        dev = self.sess.device
+        image = torch.as_tensor(image).to(device=dev, dtype=torch.float32)
+        depth = torch.as_tensor(depth).to(device=dev, dtype=torch.float32)
+        if depth.dim() == 3 and depth.shape[-1] == 1:
+            depth = depth[..., 0]
+        if image.dim() != 3 or image.shape[-1] != 3 or tuple(depth.shape) != tuple(image.shape[:2]):
+            raise ValueError('infer_full: image must be [H,W,3] and depth [H,W] or [H,W,1], got %s and %s'
+                             % (tuple(image.shape), tuple(depth.shape)))
+        return image, depth
+
+    def _full_buffers(self, H, W, stride, grid):
+        """Frame-sized buffers, allocated once per (H, W, stride): the frame itself, the patch store of n_chunks * B
+        slots, the two canvases and the RMSE workspace (fixed addresses: the chunk body is graph-captured)."""
+        key = (H, W, stride)
+        if key in self._full:
+            return self._full[key]
+        dev, B = self.sess.device, self.B
+        n_chunks = -(-grid.patches // B)
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        fb = self._full[key] = _FullBuffers(
+            n_chunks=n_chunks, slots=n_chunks * B, image=f32(H, W, 3), depth=f32(H, W), chunk=torch.zeros(1, dtype=torch.int32, device=dev),
+            store_yhat=f32(n_chunks * B, CROP, CROP), store_ybar=f32(n_chunks * B), yhat=f32(H, W), g=f32(H, W),
+            rmse=torch.zeros(1, dtype=torch.float64, device=dev), rmse_ws=torch.zeros(FULL_RMSE_BLOCKS, dtype=torch.float64, device=dev))
+        return fb
+
+    def _full_chunk(self, fb, H, W, stride):
+        """One chunk: its windows into the staging buffers, infer()'s path, its outputs into the store; advances fb.chunk."""
+        _lib.call('tdg_cgan_full_gather', K.ptr(fb.image), K.ptr(fb.depth), H, W, stride, K.ptr(fb.chunk), self.B,
+                  K.ptr(self.x_stage), K.ptr(self.y_stage), K.stream())
+        self._inputs(self.inf_ybar, self.inf_crop)
+        self._generate(self.inf_ybar, self.inf_yhat)
+        _lib.call('tdg_cgan_full_store', K.ptr(self.inf_yhat), K.ptr(self.inf_ybar) if self.version != 0 else None, self.B, fb.slots,
+                  K.ptr(fb.chunk), K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), K.stream())
+
+
+class _FullBuffers:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class FullFrame:
+    """infer_full's result: y_hat / g canvases (device f32 [H,W]), rmse (float), patches (P) and grid (cols, rows)."""
+
+    def __init__(self, y_hat, g, rmse, patches, grid):
+        self.y_hat, self.g, self.rmse, self.patches, self.grid = y_hat, g, rmse, patches, grid
+
+    def __repr__(self):
+        return 'FullFrame(%dx%d, patches=%d, grid=%s, rmse=%.6g)' % (self.y_hat.shape[0], self.y_hat.shape[1], self.patches,
+                                                                     self.grid, self.rmse)
+
+
+class PatchGrid(tuple):
+    """(cols, rows) of the window grid of paper_fullimage.py's build_batch (:90-110), with the patch count and corners."""
+
+    def __new__(cls, cols, rows, stride):
+        t = tuple.__new__(cls, (cols, rows))
+        t.stride = stride
+        return t
+
+    cols = property(lambda self: self[0])
+    rows = property(lambda self: self[1])
+    patches = property(lambda self: self[0] * self[1])
+
+    def corner(self, c):
+        """(top, left) of patch c: c = n * cols + m with n over rows (outer) and m over cols (inner) -> (m s, n s)."""
+        if not 0 <= c < self.patches:
+            raise IndexError('patch %d of %d' % (c, self.patches))
+        n, m = divmod(c, self.cols)
+        return m * self.stride, n * self.stride
+
+
+def patch_grid(H, W, stride):
+    """cols = (H - 93) // s windows down, rows = (W - 93) // s across (the reference's int((side - 65 - 29 + 1) / s)).
+    ValueError for a frame smaller than 94 x 94 or a stride below 1; a grid may be empty (stride beyond the frame)."""
+    H, W, stride = int(H), int(W), int(stride)
+    if H < FULL_MIN_SIDE or W < FULL_MIN_SIDE:
+        raise ValueError('patch_grid: a %dx%d frame is smaller than %dx%d' % (H, W, FULL_MIN_SIDE, FULL_MIN_SIDE))
+    if stride < 1:
+        raise ValueError('patch_grid: stride %d < 1' % stride)
+    span = SRC + CROP - 1
+    return PatchGrid((H - span) // stride, (W - span) // stride, stride)
 
 
 # ------------------------------------------------------------------------------------------------------

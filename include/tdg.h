@@ -315,6 +315,32 @@ int tdg_cgan_wgan_loss(int dtype, const void* logits, int rows, int cs, int mode
 int tdg_cgan_metrics(const float* y, const float* pred, const float* offset, int n, int hw, unsigned long long* counts, float* out,
                      void* workspace, size_t workspace_bytes, void* stream);
 size_t tdg_cgan_metrics_workspace_bytes(void);
+/* ---- paper_cgan full-frame inference (paper_fullimage.py; 3dgan_amd/csrc/tdg_cgan_full.hip) ----------------------------
+ * The 65x65 window slides over an H x W frame at stride s (build_batch, :90-110): cols = (H - 93) / s windows down,
+ * rows = (W - 93) / s across, P = cols * rows; patch c = n * cols + m (n < rows outer, m < cols inner) has its top-left
+ * corner at (m s, n s).  H, W >= 94 and s >= 1 or TDG_EINVAL.  The chunk index is a device int, so that a captured chunk
+ * body (gather -> model -> store) replays as the next chunk.
+ * tdg_cgan_full_gather: image f32 [H,W,3] and depth f32 [H,W] -> x_stage f32 [batch,65,65,3] and y_stage f32 [batch,65,65,1]:
+ *   slot b holds patch c = chunk[0] * batch + b, zeros where c >= P (the reference's zero padding).  A pure copy. */
+int tdg_cgan_full_gather(const float* image, const float* depth, int H, int W, int stride, const int* chunk, int batch,
+                         float* x_stage, float* y_stage, void* stream);
+/* tdg_cgan_full_store: yhat f32 [batch,29,29] and ybar f32 [batch] (nullable: zeros, the baseline's g = y_hat) to slots
+ * [chunk[0] * batch, chunk[0] * batch + batch) of store_yhat f32 [slots,29,29] / store_ybar f32 [slots]; then chunk[0] += 1
+ * (a second launch).  A chunk that would pass `slots` writes nothing but still advances. */
+int tdg_cgan_full_store(const float* yhat, const float* ybar, int batch, long long slots, int* chunk, float* store_yhat,
+                        float* store_ybar, void* stream);
+/* tdg_cgan_full_blend: the ordered blend of reconstruct (:126-155), one launch.  Patch c's 29x29 block lands at
+ * (m s + offset, n s + offset) (offset in [0, 36]; the reference places it at 18).  Per pixel, over the covering patches in
+ * ascending c, in float64: the first sets v = d, every later one v = (v + d) / 2; uncovered pixels are 0 (nan_to_num).
+ *   canvas_yhat f32 [H,W] from d = store_yhat; canvas_g f32 [H,W] from d = store_yhat - store_ybar (f32).
+ * Each canvas is bit-equal to the float64 recurrence cast to f32.  P > slots is TDG_EINVAL. */
+int tdg_cgan_full_blend(const float* store_yhat, const float* store_ybar, long long slots, int H, int W, int stride, int offset,
+                        float* canvas_yhat, float* canvas_g, void* stream);
+/* tdg_cgan_full_rmse: out[0] = sqrt(mean((double(10 depth) - canvas)^2)) (f64) over rows [18, H-46) and columns [18, W-46)
+ * of depth f32 [H,W] (10 depth rounded in f32, as the reference) and canvas f32 [H,W] (:157-163).  Per-block f64 partials
+ * in a workspace of at least 256 doubles, finished in block order by a second launch: deterministic. */
+int tdg_cgan_full_rmse(const float* depth, const float* canvas, int H, int W, double* out, void* workspace, size_t workspace_bytes,
+                       void* stream);
 /* ---- VAE pieces (models/vae.py:66-90,113-129) -------------------------------------------------------
  * heads = [z_mean | z_stddev] rows of 2L (channel stride hs); z = mean + stddev * eps (models/vae.py:128) */
 int tdg_vae_reparam(int dtype, const void* heads, int hs, const void* eps, int es, int rows, int L, void* z, int zs,
