@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/tdg.h"
 
 typedef __bf16 bf16_t;
@@ -38,6 +40,27 @@ void tdg_timing_stop(hipStream_t s);
       return TDG_EHIP;                                                      \
     }                                                                       \
   } while (0)
+
+// One kernel launch of a conv entry point.  K's dynamic-LDS limit is raised to max_lds once per process (K = nullptr: the
+// default limit).  `name` is noted for tdg_last_kernel (note = false: an auxiliary pass, which leaves the GEMM's name in
+// place).  `launch` enqueues the kernel, plus any kernel that finishes its work, inside one tdg_timing_* window; then the
+// launch is checked.  `name` must stay valid: a literal or a TDG_NAME buffer.
+template <auto K = nullptr, class L>
+int tdg_launch(const char* name, int max_lds, double flops, hipStream_t s, L&& launch, bool note = true) {
+  if constexpr (!std::is_null_pointer_v<decltype(K)>) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    (void)attr;
+  }
+  if (note) tdg_note_kernel(name);
+  tdg_timing_start(name, flops, s);
+  launch();
+  tdg_timing_stop(s);
+  TDG_HIP_LAUNCH_CHECK(name);
+  return TDG_OK;
+}
+// a kernel variant's name, formatted once per call site and template instantiation of the enclosing launcher
+#define TDG_NAME(...) \
+  [&]() -> const char* { static char n_[64] = ""; if (!n_[0]) snprintf(n_, sizeof(n_), __VA_ARGS__); return n_; }()
 
 static inline int tdg_dtype_size(int dtype) { return dtype == TDG_BF16 ? 2 : 4; }
 static inline int tdg_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }

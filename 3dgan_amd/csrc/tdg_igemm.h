@@ -47,7 +47,7 @@ struct IgArgs {
   FastDiv fd_c;          // divide by C (scalar path) or by C/VEC (vector path)
   // K order of the packed filter on the vector path: K chunk (16 bytes) index = (slice * ntaps + tap) * ckv + j with
   // ckv = fd_ck.d chunks of a tap's channels per slice, channel vector cv = slice * ckv + j.  nslices = 1 (ckv = C/VEC)
-  // is the plain (tap, channel) order; a sliced filter (tdg_k_slice_chunks) lets igemm_fwd_patch_kernel keep a
+  // is the plain (tap, channel) order; a sliced filter (k_slice_chunks, via plan_fwd / plan_bwd_data) lets igemm_fwd_patch_kernel keep a
   // channel slice of the gathered operand resident in LDS across all the taps that read it.
   FastDiv fd_ck;
   int nslices;

@@ -3303,12 +3303,6 @@ __global__ void __launch_bounds__(256, 2) thin_fwd_kernel(const ThinFwdArgs a) {
 // ============================================================================================
 namespace {
 
-thread_local double t_flops = 0.0;   // algorithmic FLOPs of the entry-point call being dispatched (for tdg_timing_*)
-thread_local const TdgEpilogue* t_col = nullptr;   // column-partial request of the call being dispatched (fill_epilogue)
-thread_local const TdgEpilogue* t_splitk = nullptr;   // epilogue carrying a split-K workspace (fill_epilogue)
-
-struct TileCfg { int bm, bn; };
-
 inline int pick_bn(int n) {
   if (n <= 16) return 16;
   if (n <= 64) return 64;
@@ -3316,61 +3310,55 @@ inline int pick_bn(int n) {
   return w208 < w128 - 1e-9 ? 208 : 128;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN>
-int launch_fwd_cfg(const IgArgs& a, bool veca, int grid_x, int nclasses, hipStream_t s) {
-  const size_t lds = (size_t)(BM + BN) * IG_BKB + IG_MAX_TAPS * sizeof(int);
-  dim3 grid(grid_x, 1, nclasses), block(256);
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_fwd_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BM, BN);
-  tdg_note_kernel(name);
-  tdg_timing_start(name, t_flops, s);
-  if (veca)
-    hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, true>), grid, block, lds, s, a);
-  else
-    hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, false>), grid, block, lds, s, a);
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_fwd");
-  return TDG_OK;
+#ifdef TDG_STAMPS
+// diagnostic library only: where the stamping kernels write their per-wave cycle sums
+inline unsigned long long* stamp_ptr() {
+  return getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
+}
+#endif
+
+// Column partials of the stored tile (TdgEpilogue.col_partial) for a launch whose kernel writes them: granted when the caller
+// asked for them and the buffer holds every row tile.  Otherwise *col_nblk_out keeps the 0 that set_epilogue wrote.
+void grant_col_partial(IgArgs& a, const TdgEpilogue* epi) {
+  if (!epi || !epi->col_partial || epi->col_mode == TDG_COL_NONE || !epi->col_nblk_out) return;
+  const int nblk = a.nclasses * a.ntiles_m_max;
+  if ((size_t)nblk * 2 * a.N * sizeof(float) > epi->col_partial_bytes) return;
+  a.col_partial = epi->col_partial;
+  a.col_mode = epi->col_mode;
+  a.col_images = epi->col_images;
+  *epi->col_nblk_out = nblk;
 }
 
-// columns [n_begin, n_begin + ntiles_n * BN) of the problem (clipped to N)
+template <typename T, int BM, int BN, int WGM, int WGN>
+int launch_fwd_cfg(const IgArgs& a, bool veca, int grid_x, double flops, hipStream_t s) {
+  const size_t lds = (size_t)(BM + BN) * IG_BKB + IG_MAX_TAPS * sizeof(int);
+  const dim3 grid(grid_x, 1, a.nclasses), block(256);
+  const char* name = TDG_NAME("igemm_fwd_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BM, BN);
+  return tdg_launch(name, 0, flops, s, [&] {
+    if (veca)
+      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, true>), grid, block, lds, s, a);
+    else
+      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, false>), grid, block, lds, s, a);
+  });
+}
+
 template <typename T, int BM, int BN, int NS, int NW = 8, int WS = 0>
-int launch_fwd_dma(IgArgs& a, int mmax, hipStream_t s, int n_begin = 0, int ntiles_n = -1) {
-  a.n_begin = n_begin;
-  a.ntiles_n = ntiles_n < 0 ? tdg_ceil_div(a.N, BN) : ntiles_n;
+int launch_fwd_dma(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
+  a.n_begin = 0;
+  a.ntiles_n = tdg_ceil_div(a.N, BN);
   a.ntiles_m_max = tdg_ceil_div(mmax, BM);
-  if (t_col && sizeof(T) == 2 && !a.accumulate && (a.N & 3) == 0 && n_begin == 0 && a.ntiles_n * BN >= a.N) {
-    const int nblk = a.nclasses * a.ntiles_m_max;
-    if ((size_t)nblk * 2 * a.N * sizeof(float) <= t_col->col_partial_bytes) {
-      a.col_partial = t_col->col_partial;
-      a.col_mode = t_col->col_mode;
-      a.col_images = t_col->col_images;
-      *t_col->col_nblk_out = nblk;
-    }
-  }
+  if (sizeof(T) == 2 && !a.accumulate && (a.N & 3) == 0) grant_col_partial(a, epi);
   constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
   const size_t lds = NS * (size_t)(BM + BNL) * IG_BKB + IG_MAX_TAPS * sizeof(int) + BNL * sizeof(float);   // ring, taps, bias row
   static_assert(NS * (size_t)(BM + BNL) * IG_BKB + IG_MAX_TAPS * sizeof(int) + BNL * sizeof(float) <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), WS ? "igemm_fwd_dma_kernel<%s,%d,%d,%d,8,1>" : (NW == 8 ? "igemm_fwd_dma_kernel<%s,%d,%d,%d>" : "igemm_fwd_dma_kernel<%s,%d,%d,%d,4,0>"), sizeof(T) == 2 ? "bf16" : "f32", BM, BN, NS);
-  tdg_note_kernel(name);
-  const int n_end = n_begin + a.ntiles_n * BN < a.N ? n_begin + a.ntiles_n * BN : a.N;
   // split-K: a grid that leaves most of the chip idle (pix2pix's 1x1 ... 8x8 bottleneck layers: 4 - 32 workgroups, each
   // walking 128 - 256 K steps) is cut along K into f32 partial tiles, finished by splitk_finish_kernel
-  a.ksplit = 1;
-  a.steps_per_split = 1 << 30;
-  a.slab = nullptr;
   a.slab_rows = a.ntiles_m_max * BM;
   int smax = 0;
   for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
   const long long wgs = (long long)a.ntiles_n * a.ntiles_m_max * a.nclasses;
   const int ks_force = getenv("TDG_KSPLIT") ? atoi(getenv("TDG_KSPLIT")) : 0;                  // diagnostics: 1 = never, n = n splits
-  if (!WS && t_splitk && t_splitk->splitk_ws && wgs <= 128 && smax >= 16 && n_begin == 0 && a.ntiles_n * BN >= a.N && ks_force != 1) {
+  if (!WS && epi && epi->splitk_ws && epi->splitk_ws_bytes && wgs <= 128 && smax >= 16 && ks_force != 1) {
     int want = (int)(256 / wgs);
     if (want > smax / 4) want = smax / 4;                    // >= 4 steps per split
     if (want > 8) want = 8;                                  // measured (64 images, 512 -> 512, 4x4 s2): 2x2 / 4x4 inputs 0.019 / 0.020 ms at 8 splits, 0.026 / 0.032 at 32
@@ -3378,26 +3366,25 @@ int launch_fwd_dma(IgArgs& a, int mmax, hipStream_t s, int n_begin = 0, int ntil
     const int per = tdg_ceil_div(smax, want);
     const int nsplit = tdg_ceil_div(smax, per);
     const size_t need = (size_t)nsplit * a.nclasses * a.slab_rows * a.N * sizeof(float);
-    if (nsplit > 1 && need <= t_splitk->splitk_ws_bytes) {
+    if (nsplit > 1 && need <= epi->splitk_ws_bytes) {
       a.ksplit = nsplit;
       a.steps_per_split = per;
-      a.slab = static_cast<float*>(t_splitk->splitk_ws);
+      a.slab = static_cast<float*>(epi->splitk_ws);
       a.col_partial = nullptr;                               // (the partial tiles are not the stored tile)
-      if (t_col) *t_col->col_nblk_out = 0;
+      if (epi->col_nblk_out) *epi->col_nblk_out = 0;
     }
   }
-  dim3 grid(a.ntiles_n * a.ntiles_m_max, a.ksplit, a.nclasses), block(64 * NW);
-  tdg_timing_start(name, t_flops * (double)(n_end - n_begin) / (double)a.N, s);
-  hipLaunchKernelGGL((igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>), grid, block, lds, s, a);
-  if (a.ksplit > 1) {
-    int mmx = 0;
-    for (int c = 0; c < a.nclasses; ++c) mmx = a.cls[c].M > mmx ? a.cls[c].M : mmx;
-    const long long items = (long long)mmx * ((a.N + 3) / 4);
-    hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)((items + 255) / 256), 1, a.nclasses), dim3(256), 0, s, a);
-  }
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_fwd_dma");
-  return TDG_OK;
+  const dim3 grid(a.ntiles_n * a.ntiles_m_max, a.ksplit, a.nclasses), block(64 * NW);
+  const char* name = TDG_NAME(WS ? "igemm_fwd_dma_kernel<%s,%d,%d,%d,8,1>" : (NW == 8 ? "igemm_fwd_dma_kernel<%s,%d,%d,%d>" : "igemm_fwd_dma_kernel<%s,%d,%d,%d,4,0>"), sizeof(T) == 2 ? "bf16" : "f32", BM, BN, NS);
+  return tdg_launch<igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>>(name, (int)lds, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>), grid, block, lds, s, a);
+    if (a.ksplit > 1) {
+      int mmx = 0;
+      for (int c = 0; c < a.nclasses; ++c) mmx = a.cls[c].M > mmx ? a.cls[c].M : mmx;
+      const long long items = (long long)mmx * ((a.N + 3) / 4);
+      hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)((items + 255) / 256), 1, a.nclasses), dim3(256), 0, s, a);
+    }
+  });
 }
 
 // igemm_fwd_patch_kernel: does it apply to this launch?  Fills the tap groups / lattice of every class when it does.
@@ -3485,66 +3472,38 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
 }
 
 template <int BM, int BN, int CK = PT_CK, int PIECES = PT_PIECES>
-int launch_fwd_patch(IgArgs& a, int mmax, hipStream_t s) {
+int launch_fwd_patch(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
   a.n_begin = 0;
   a.ntiles_n = tdg_ceil_div(a.N, BN);
   a.ntiles_m_max = tdg_ceil_div(mmax, BM);
-  if (t_col) {
-    const int nblk = a.nclasses * a.ntiles_m_max;
-    if ((size_t)nblk * 2 * a.N * sizeof(float) <= t_col->col_partial_bytes) {
-      a.col_partial = t_col->col_partial;
-      a.col_mode = t_col->col_mode;
-      a.col_images = t_col->col_images;
-      *t_col->col_nblk_out = nblk;
-    }
-  }
-  a.ksplit = 1;
-  a.steps_per_split = 1 << 30;
-  a.slab = nullptr;
+  grant_col_partial(a, epi);
   int smax = 0;
   for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
   constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
   const size_t lds = PT_ZEROB + 3 * (size_t)BNL * IG_BKB + PT_NPB * (size_t)PIECES * 1024 + (size_t)smax * 64 + BNL * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_patch_kernel<BM, BN, 0, CK, PIECES>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#ifdef TDG_STAMPS
-    if constexpr (BM == 192) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_patch_kernel<BM, BN, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_patch_kernel<BM, BN, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_patch_kernel<BM, BN, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_patch_kernel<BM, BN, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    attr_set = true;
-  }
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_fwd_patch_kernel<bf16,%d,%d>", BM, BN);
-  tdg_note_kernel(name);
-  dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
   if (lds > 160 * 1024) {
     tdg_set_error("igemm_fwd_patch: %zu bytes of LDS", lds);
     return TDG_EUNSUPPORTED;
   }
-  tdg_timing_start(name, t_flops, s);
+  const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
+  const char* name = TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d>", BM, BN);
+  auto go = [&](auto abl) {
+    constexpr int ABL = decltype(abl)::value;
+    return tdg_launch<igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES>>(name, 160 * 1024, flops, s, [&] {
+      hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES>), grid, block, lds, s, a);
+    });
+  };
 #ifdef TDG_STAMPS
   // ablation instantiations (their results are garbage): compiled into the diagnostic library (build.sh stamps) only
-  const int abl = (BM == 192 && getenv("TDG_PATCH_ABL")) ? atoi(getenv("TDG_PATCH_ABL")) : 0;
   if constexpr (BM == 192) {
-    if (abl == 1) hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 1>), grid, block, lds, s, a);
-    else if (abl == 2) hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 2>), grid, block, lds, s, a);
-    else if (abl == 3) hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 3>), grid, block, lds, s, a);
-    else if (abl == 4) hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 4>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 0>), grid, block, lds, s, a);
-  } else {
-    hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 0, CK, PIECES>), grid, block, lds, s, a);
+    const int abl = getenv("TDG_PATCH_ABL") ? atoi(getenv("TDG_PATCH_ABL")) : 0;
+    if (abl == 1) return go(IntC<1>{});
+    if (abl == 2) return go(IntC<2>{});
+    if (abl == 3) return go(IntC<3>{});
+    if (abl == 4) return go(IntC<4>{});
   }
-#else
-  hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, 0, CK, PIECES>), grid, block, lds, s, a);
 #endif
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_fwd_patch");
-  return TDG_OK;
+  return go(IntC<0>{});
 }
 
 // igemm_fwd_bp_kernel: the block-patch plan (on a copy: the classes are rewritten only when everything holds) plus what the
@@ -3569,22 +3528,11 @@ bool plan_fwd_bp(IgArgs& a, int mmax) {
 }
 
 template <int BN>
-int launch_fwd_bp(IgArgs& a, int mmax, hipStream_t s) {
+int launch_fwd_bp(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
   a.n_begin = 0;
   a.ntiles_n = tdg_ceil_div(a.N, BN);
   a.ntiles_m_max = tdg_ceil_div(mmax, 256);
-  if (t_col) {
-    const int nblk = a.nclasses * a.ntiles_m_max;
-    if ((size_t)nblk * 2 * a.N * sizeof(float) <= t_col->col_partial_bytes) {
-      a.col_partial = t_col->col_partial;
-      a.col_mode = t_col->col_mode;
-      a.col_images = t_col->col_images;
-      *t_col->col_nblk_out = nblk;
-    }
-  }
-  a.ksplit = 1;
-  a.steps_per_split = 1 << 30;
-  a.slab = nullptr;
+  grant_col_partial(a, epi);
   int smax = 0;
   for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
   const size_t lds = PT_ZEROB + 3 * (size_t)BN * IG_BKB + PT_NPB * (size_t)BP_PIECES * 1024 + 1024 + (size_t)smax * 8 + BN * sizeof(float);
@@ -3592,27 +3540,17 @@ int launch_fwd_bp(IgArgs& a, int mmax, hipStream_t s) {
     tdg_set_error("igemm_fwd_bp: %zu bytes of LDS", lds);
     return TDG_EUNSUPPORTED;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fwd_bp_kernel<BN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
 #ifdef TDG_STAMPS
-  a.stamps = getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
+  a.stamps = stamp_ptr();
 #endif
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_fwd_bp_kernel<bf16,256,%d>", BN);
-  tdg_note_kernel(name);
-  dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
-  tdg_timing_start(name, t_flops, s);
-  hipLaunchKernelGGL((igemm_fwd_bp_kernel<BN>), grid, block, lds, s, a);
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_fwd_bp");
-  return TDG_OK;
+  const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
+  return tdg_launch<igemm_fwd_bp_kernel<BN>>(TDG_NAME("igemm_fwd_bp_kernel<bf16,256,%d>", BN), 160 * 1024, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_fwd_bp_kernel<BN>), grid, block, lds, s, a);
+  });
 }
 
 template <typename T>
-int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
+int launch_fwd(IgArgs& a, bool veca, int bn, double flops, const TdgEpilogue* epi, hipStream_t s) {
   constexpr int BM = 128;
 #ifdef TDG_STAMPS
   static const int dbg = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;   // loop ablations (garbage results): diagnostic library only
@@ -3623,7 +3561,7 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
   const int dma_mode = dma_env ? atoi(dma_env) : 1;
   a.debug = dbg;
 #ifdef TDG_STAMPS
-  a.stamps = getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
+  a.stamps = stamp_ptr();
 #endif
   int mmax = 0;
   for (int c = 0; c < a.nclasses; ++c) mmax = a.cls[c].M > mmax ? a.cls[c].M : mmax;
@@ -3640,9 +3578,9 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
       const double c128 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 128), 256) * 128 / 0.75;   // in the step: 890 - 915 TF against 1170 - 1370
       const int pbm = getenv("TDG_PATCH_BM") ? atoi(getenv("TDG_PATCH_BM")) : 0;            // diagnostics: force a row tile
       const bool want128 = pbm ? pbm == 128 : c128 < c192 - 1e-9;
-      if (want128 && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, s);
-      if (plan_fwd_patch<192>(a, mmax)) return launch_fwd_patch<192, 208>(a, mmax, s);
-      if (!want128 && !pbm && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, s);
+      if (want128 && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
+      if (plan_fwd_patch<192>(a, mmax)) return launch_fwd_patch<192, 208>(a, mmax, flops, epi, s);
+      if (!want128 && !pbm && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
     }
   }
   if (veca && bn == 208 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0) {
@@ -3675,16 +3613,16 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
       const char* n112_env = getenv("TDG_FWD_N112");            // diagnostics: 0 = never, 1 = 128-row tiles only
       if (per * tdg_ceil_div(mmax, 128) <= 128 && a.N > 112 && !(n112_env && atoi(n112_env) == 0)) {
         const long long wg112 = (long long)tdg_ceil_div(a.N, 112) * a.nclasses * tdg_ceil_div(mmax, 128);
-        if (wg112 <= 128 && !(n112_env && atoi(n112_env) == 1)) return launch_fwd_dma<T, 64, 112, 3>(a, mmax, s);   // still half empty
-        return launch_fwd_dma<T, 128, 112, 3>(a, mmax, s);
+        if (wg112 <= 128 && !(n112_env && atoi(n112_env) == 1)) return launch_fwd_dma<T, 64, 112, 3>(a, mmax, flops, epi, s);   // still half empty
+        return launch_fwd_dma<T, 128, 112, 3>(a, mmax, flops, epi, s);
       }
       if constexpr (sizeof(T) == 2) {
         const char* nw_env = getenv("TDG_DMA_NW");          // diagnostics: 8 = every wave loads and computes
         const char* ws128_env = getenv("TDG_WS128");        // diagnostics: 0 = only the 192-row tile is specialised
         if (!a.accumulate && !(nw_env && atoi(nw_env) != 44) && !(ws128_env && atoi(ws128_env) == 0))
-          return launch_fwd_dma<T, 128, 208, 3, 8, 1>(a, mmax, s);
+          return launch_fwd_dma<T, 128, 208, 3, 8, 1>(a, mmax, flops, epi, s);
       }
-      return launch_fwd_dma<T, 128, 208, 3>(a, mmax, s);
+      return launch_fwd_dma<T, 128, 208, 3>(a, mmax, flops, epi, s);
     }
     // 192-row tile, bf16, staged epilogue: the wave-specialised form (4 compute + 4 loader waves; measured +5 % on
     // these launches inside the training step).  TDG_DMA_NW (diagnostics): 8 = every wave loads and computes
@@ -3692,9 +3630,9 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
     const char* nw_env = getenv("TDG_DMA_NW");
     const int nw192 = nw_env ? atoi(nw_env) : 44;
     if constexpr (sizeof(T) == 2)
-      if (bm == 192 && nw192 == 44 && !a.accumulate && ring192 != 2) return launch_fwd_dma<T, 192, 208, 3, 8, 1>(a, mmax, s);
-    if (bm == 192) return ring192 == 2 ? launch_fwd_dma<T, 192, 208, 2>(a, mmax, s) : launch_fwd_dma<T, 192, 208, 3>(a, mmax, s);
-    return launch_fwd_dma<T, 256, 208, 2>(a, mmax, s);
+      if (bm == 192 && nw192 == 44 && !a.accumulate && ring192 != 2) return launch_fwd_dma<T, 192, 208, 3, 8, 1>(a, mmax, flops, epi, s);
+    if (bm == 192) return ring192 == 2 ? launch_fwd_dma<T, 192, 208, 2>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 192, 208, 3>(a, mmax, flops, epi, s);
+    return launch_fwd_dma<T, 256, 208, 2>(a, mmax, flops, epi, s);
   }
   // 128-column problems (pix2pix / VAE widths 128, 256, 512, 1024) and 65..112 columns (the generator's 100-channel
   // layers, a 7-tile-wide column tile): the same LDS-DMA kernel, 3-stage ring at every row tile
@@ -3703,10 +3641,10 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
   // slices, 28 KiB patches>): 16 + 13 KB (128 columns) / 8 + 13 KB (64) of intake per K step instead of 16 + 32 / 8 + 16
   if constexpr (sizeof(T) == 2) {
     if (veca && dma_mode == 1 && (bn == 128 || bn == 64) && !getenv("TDG_DMA_BM") && !getenv("TDG_DMA_NW")) {
-      if (bn == 128 && a.N > 112 && plan_fwd_bp<128>(a, mmax)) return launch_fwd_bp<128>(a, mmax, s);
-      if (bn == 64 && a.N > 32 && plan_fwd_bp<64>(a, mmax)) return launch_fwd_bp<64>(a, mmax, s);
-      if (bn == 128 && a.N > 112 && plan_fwd_patch<256, 128, 4, 28>(a, mmax)) return launch_fwd_patch<256, 128, 4, 28>(a, mmax, s);
-      if (bn == 64 && a.N > 32 && plan_fwd_patch<256, 64, 4, 28>(a, mmax)) return launch_fwd_patch<256, 64, 4, 28>(a, mmax, s);
+      if (bn == 128 && a.N > 112 && plan_fwd_bp<128>(a, mmax)) return launch_fwd_bp<128>(a, mmax, flops, epi, s);
+      if (bn == 64 && a.N > 32 && plan_fwd_bp<64>(a, mmax)) return launch_fwd_bp<64>(a, mmax, flops, epi, s);
+      if (bn == 128 && a.N > 112 && plan_fwd_patch<256, 128, 4, 28>(a, mmax)) return launch_fwd_patch<256, 128, 4, 28>(a, mmax, flops, epi, s);
+      if (bn == 64 && a.N > 32 && plan_fwd_patch<256, 64, 4, 28>(a, mmax)) return launch_fwd_patch<256, 64, 4, 28>(a, mmax, flops, epi, s);
     }
   }
   if (veca && bn == 128 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0) {
@@ -3718,11 +3656,11 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
     //  638 vs 709 TF (112 columns, the generator's dc3 at 2560 images): the smaller tile's intake per FLOP costs more than the
     //  overlap returns.  Not kept.)
     const double c256 = (double)tdg_ceil_div(t256, 256) * 256, c128 = (double)tdg_ceil_div(t128, 256) * 128 / 0.85;
-    if (bnt == 112) return c128 < c256 ? launch_fwd_dma<T, 128, 112, 3>(a, mmax, s) : launch_fwd_dma<T, 256, 112, 3>(a, mmax, s);
-    return c128 < c256 ? launch_fwd_dma<T, 128, 128, 3>(a, mmax, s) : launch_fwd_dma<T, 256, 128, 3>(a, mmax, s);
+    if (bnt == 112) return c128 < c256 ? launch_fwd_dma<T, 128, 112, 3>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 256, 112, 3>(a, mmax, flops, epi, s);
+    return c128 < c256 ? launch_fwd_dma<T, 128, 128, 3>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 256, 128, 3>(a, mmax, flops, epi, s);
   }
   // 64-column problems: 128-row tile (3 loader pieces per wave on 4 column tiles)
-  if (veca && bn == 64 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0 && a.N > 32) return launch_fwd_dma<T, 128, 64, 3>(a, mmax, s);
+  if (veca && bn == 64 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0 && a.N > 32) return launch_fwd_dma<T, 128, 64, 3>(a, mmax, flops, epi, s);
   a.ntiles_n = tdg_ceil_div(a.N, bn);
   a.ntiles_m_max = tdg_ceil_div(mmax, BM);
   int gx = a.ntiles_n * a.ntiles_m_max;
@@ -3730,65 +3668,52 @@ int launch_fwd(IgArgs& a, bool veca, int bn, hipStream_t s) {
   if (bn == 208 && (long long)gx * a.nclasses < 384) {
     a.ntiles_m_max = tdg_ceil_div(mmax, 64);
     gx = a.ntiles_n * a.ntiles_m_max;
-    return launch_fwd_cfg<T, 64, 208, 4, 1>(a, veca, gx, a.nclasses, s);
+    return launch_fwd_cfg<T, 64, 208, 4, 1>(a, veca, gx, flops, s);
   }
   switch (bn) {
-    case 16: return launch_fwd_cfg<T, BM, 16, 4, 1>(a, veca, gx, a.nclasses, s);
-    case 64: return launch_fwd_cfg<T, BM, 64, 4, 1>(a, veca, gx, a.nclasses, s);
-    case 128: return launch_fwd_cfg<T, BM, 128, 2, 2>(a, veca, gx, a.nclasses, s);
-    case 208: return launch_fwd_cfg<T, BM, 208, 4, 1>(a, veca, gx, a.nclasses, s);
+    case 16: return launch_fwd_cfg<T, BM, 16, 4, 1>(a, veca, gx, flops, s);
+    case 64: return launch_fwd_cfg<T, BM, 64, 4, 1>(a, veca, gx, flops, s);
+    case 128: return launch_fwd_cfg<T, BM, 128, 2, 2>(a, veca, gx, flops, s);
+    case 208: return launch_fwd_cfg<T, BM, 208, 4, 1>(a, veca, gx, flops, s);
   }
   tdg_set_error("igemm_fwd: no tile config for BN=%d", bn);
   return TDG_EUNSUPPORTED;
 }
 
 template <typename T, int BKK, int BN, int WGK, int WGN>
-int launch_wgrad_cfg(const WgArgs& a, bool veca, hipStream_t s) {
+int launch_wgrad_cfg(const WgArgs& a, bool veca, double flops, hipStream_t s) {
   constexpr int MR = WgGeom<T>::MR;
   const size_t lds = (size_t)MR * (WgGeom<T>::pitch(BKK) + WgGeom<T>::pitch(BN)) + IG_MAX_TAPS * sizeof(int);
-  dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(256);
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_wgrad_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BKK, BN);
-  tdg_note_kernel(name);
-  tdg_timing_start(name, t_flops, s);
-  if (veca)
-    hipLaunchKernelGGL((igemm_wgrad_kernel<T, BKK, BN, WGK, WGN, true>), grid, block, lds, s, a);
-  else
-    hipLaunchKernelGGL((igemm_wgrad_kernel<T, BKK, BN, WGK, WGN, false>), grid, block, lds, s, a);
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_wgrad");
-  return TDG_OK;
+  const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(256);
+  const char* name = TDG_NAME("igemm_wgrad_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BKK, BN);
+  return tdg_launch(name, 0, flops, s, [&] {
+    if (veca)
+      hipLaunchKernelGGL((igemm_wgrad_kernel<T, BKK, BN, WGK, WGN, true>), grid, block, lds, s, a);
+    else
+      hipLaunchKernelGGL((igemm_wgrad_kernel<T, BKK, BN, WGK, WGN, false>), grid, block, lds, s, a);
+  });
 }
 
 template <int BN, int MODE>
-int launch_wgrad_dma(WgArgs& a, hipStream_t s) {
+int launch_wgrad_dma(WgArgs& a, double flops, hipStream_t s) {
   const size_t lds = 4 * (size_t)WD_MR * WD_ROWB + IG_MAX_TAPS * sizeof(int);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_dma_kernel<BN, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_wgrad_dma_kernel<bf16,256,%d,%d>", BN, MODE);
-  dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(512);
-  tdg_note_kernel(name);
+  const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(512);
 #ifdef TDG_STAMPS
-  a.stamps = getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
+  a.stamps = stamp_ptr();
 #endif
-  tdg_timing_start(name, t_flops, s);
-  hipLaunchKernelGGL((igemm_wgrad_dma_kernel<BN, MODE>), grid, block, lds, s, a);
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_wgrad_dma");
-  return TDG_OK;
+  const char* name = TDG_NAME("igemm_wgrad_dma_kernel<bf16,256,%d,%d>", BN, MODE);
+  return tdg_launch<igemm_wgrad_dma_kernel<BN, MODE>>(name, (int)lds, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<BN, MODE>), grid, block, lds, s, a);
+  });
 }
 
 template <typename T>
-int launch_wgrad(WgArgs& a, bool veca, int bn, hipStream_t s) {
+int launch_wgrad(WgArgs& a, bool veca, int bn, double flops, hipStream_t s) {
   switch (bn) {
-    case 16: return launch_wgrad_cfg<T, 128, 16, 4, 1>(a, veca, s);
-    case 64: return launch_wgrad_cfg<T, 128, 64, 4, 1>(a, veca, s);
-    case 128: return launch_wgrad_cfg<T, 128, 128, 2, 2>(a, veca, s);
-    case 208: return launch_wgrad_cfg<T, 128, 208, 4, 1>(a, veca, s);
+    case 16: return launch_wgrad_cfg<T, 128, 16, 4, 1>(a, veca, flops, s);
+    case 64: return launch_wgrad_cfg<T, 128, 64, 4, 1>(a, veca, flops, s);
+    case 128: return launch_wgrad_cfg<T, 128, 128, 2, 2>(a, veca, flops, s);
+    case 208: return launch_wgrad_cfg<T, 128, 208, 4, 1>(a, veca, flops, s);
   }
   tdg_set_error("igemm_wgrad: no tile config for BN=%d", bn);
   return TDG_EUNSUPPORTED;
@@ -3906,7 +3831,7 @@ struct Col2imPlan {
   size_t w_bytes, lds;
 };
 
-bool plan_bwd_col2im(const TdgConvDesc* d, Col2imPlan* f) {
+bool plan_bwd_col2im(const TdgConvDesc* d, const BwdClassPlan* cls, Col2imPlan* f) {
   static const int enabled = getenv("TDG_COL2IM") ? atoi(getenv("TDG_COL2IM")) : 1;   // diagnostics: 0 = fused-class / per-class kernels
   if (!enabled || d->dtype != TDG_BF16 || d->stride != 2) return false;
   if (d->kh < 2 || d->kw < 2 || d->kh > 6 || d->kw > 6) return false;
@@ -3915,9 +3840,7 @@ bool plan_bwd_col2im(const TdgConvDesc* d, Col2imPlan* f) {
   if (ncol > maxcol || ncol > 80) return false;
   const int ke = eff_channels(d->k, d->ks, 8);
   if (!ke) return false;
-  BwdClassPlan cls[IG_MAX_CLASSES];
-  const int nc = plan_bwd_classes(d, cls);
-  if (nc != 4) return false;
+  const int nc = 4;                                          // (stride 2)
   int dh_lo = 1 << 20, dh_hi = -(1 << 20), dw_lo = 1 << 20, dw_hi = -(1 << 20);
   for (int i = 0; i < nc; ++i) {
     if (cls[i].ntaps > C2I_MAX_CLS_TAPS || cls[i].ntaps == 0) return false;
@@ -3960,21 +3883,19 @@ bool plan_bwd_col2im(const TdgConvDesc* d, Col2imPlan* f) {
 }
 
 // ---- fused-class backward-data (bwd_fused_kernel): when it applies and its geometry ---------------------------
+// (plan_bwd_data asks after plan_bwd_col2im: few (tap, channel) columns take GEMM + col2im)
 struct FusedPlan {
   int nhm, nwm, dh_min, dw_min, ntap, ke, KP, PP, wpitch, TA, ntr, TW, ntc, GH, GW, y_off;
   size_t w_bytes, lds;
 };
 
-bool plan_bwd_fused(const TdgConvDesc* d, FusedPlan* f) {
+bool plan_bwd_fused(const TdgConvDesc* d, const BwdClassPlan* cls, FusedPlan* f) {
   static const int enabled = getenv("TDG_FUSE") ? atoi(getenv("TDG_FUSE")) : 1;   // diagnostics: 0 = one launch-z per class
   if (!enabled || d->dtype != TDG_BF16 || d->stride != 2 || 4 * d->c > 16) return false;
   if (d->kh < 2 || d->kw < 2) return false;                  // every class needs a tap
-  Col2imPlan cp;
-  if (plan_bwd_col2im(d, &cp)) return false;                 // few (tap, channel) columns: GEMM + col2im
   const int ke = eff_channels(d->k, d->ks, 8);
   if (!ke) return false;
-  BwdClassPlan cls[IG_MAX_CLASSES];
-  const int nc = plan_bwd_classes(d, cls);
+  const int nc = 4;                                          // (stride 2)
   int dh_lo = 1 << 20, dh_hi = -(1 << 20), dw_lo = 1 << 20, dw_hi = -(1 << 20);
   for (int i = 0; i < nc; ++i)
     for (int t = 0; t < cls[i].ntaps; ++t) {
@@ -4061,85 +3982,233 @@ bool plan_fwd_thin(const TdgConvDesc* d, ThinPlan* t) {
   return t->lds <= 80 * 1024;                                  // two workgroups per CU
 }
 
+// ---- the plans: each decision about a conv's packed filter and its launch form has one owner ---------------------------
+// Forward: thin_fwd_kernel's filter layout or the implicit-GEMM one -- the K order (channels per tap, slice width, tap
+// order), the packed row pitch and the bytes.  Sizing, packing and every forward launch read the filter through it.
+struct FwdPlan {
+  bool thin;              // thin_fwd_kernel's layout (tp); the GEMM fields below are filled either way
+  ThinPlan tp;
+  int es, vec, bke;       // element bytes, elements per 16-byte vector, elements per K step
+  bool veca;              // vector gather: C = the channels rounded up to a whole vector (eff_channels)
+  int C;                  // channels per tap in K
+  int ntaps, Kp;          // Kp: packed row pitch (elements)
+  int ck;                 // K order (k_order only): 16-byte chunks of a tap's channels per K slice (veca), else C ...
+  int ord[IG_MAX_TAPS];   // ... and the taps in K order (fwd_tap_order)
+  size_t bytes;           // packed filter
+};
+
+// k_order = false (sizing) leaves the K order out: its per-call TDG_BLOCKPATCH read belongs to the pack and launch calls
+FwdPlan plan_fwd(const TdgConvDesc* d, bool k_order = true) {
+  FwdPlan p;
+  memset(&p, 0, sizeof(p));
+  p.thin = plan_fwd_thin(d, &p.tp);
+  p.es = tdg_dtype_size(d->dtype);
+  p.vec = 16 / p.es;
+  p.bke = IG_BKB / p.es;
+  const int ce = eff_channels(d->c, d->cs, p.vec);
+  p.veca = ce != 0;
+  p.C = p.veca ? ce : d->c;
+  p.ntaps = d->kh * d->kw;
+  p.Kp = (int)tdg_round_up((long long)p.ntaps * p.C, p.bke);
+  p.bytes = p.thin ? p.tp.w_bytes : (size_t)d->k * p.Kp * p.es;
+  if (k_order) {
+    p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->k) : p.C;
+    fwd_tap_order(d, p.ord);
+  }
+  return p;
+}
+
+// Backward data: GEMM + col2im, the fused-class kernel, or one implicit GEMM per output-parity class with the classes'
+// row pitches and byte offsets inside the packed filter.
+enum { BWD_CLASSES, BWD_COL2IM, BWD_FUSED };
+struct BwdDataPlan {
+  int form;                            // BWD_*
+  Col2imPlan cp;                       // BWD_COL2IM
+  FusedPlan fp;                        // BWD_FUSED
+  int nc;                              // parity classes (stride^2), the ones without taps included
+  BwdClassPlan cls[IG_MAX_CLASSES];
+  int Kp[IG_MAX_CLASSES];              // BWD_CLASSES: each class's packed row pitch (elements) ...
+  size_t off[IG_MAX_CLASSES];          // ... and the byte offset of its block
+  int es, vec, bke;
+  bool veca;                           // vector gather of the small side: C = its channels rounded up to a whole vector
+  int C;                               // channels per tap in K
+  int ck;                              // BWD_CLASSES with k_order: the K-slice width (FwdPlan.ck)
+  size_t bytes;                        // packed filter
+};
+
+BwdDataPlan plan_bwd_data(const TdgConvDesc* d, bool k_order = true) {
+  BwdDataPlan p;
+  memset(&p, 0, sizeof(p));
+  p.es = tdg_dtype_size(d->dtype);
+  p.vec = 16 / p.es;
+  p.bke = IG_BKB / p.es;
+  const int ke = eff_channels(d->k, d->ks, p.vec);
+  p.veca = ke != 0;
+  p.C = p.veca ? ke : d->k;
+  p.nc = plan_bwd_classes(d, p.cls);
+  if (plan_bwd_col2im(d, p.cls, &p.cp)) {
+    p.form = BWD_COL2IM;
+    p.bytes = p.cp.w_bytes;
+  } else if (plan_bwd_fused(d, p.cls, &p.fp)) {
+    p.form = BWD_FUSED;
+    p.bytes = p.fp.w_bytes;
+  } else {
+    p.form = BWD_CLASSES;
+    for (int i = 0; i < p.nc; ++i) {
+      p.Kp[i] = (int)tdg_round_up((long long)p.cls[i].ntaps * p.C, p.bke);
+      p.off[i] = p.bytes;
+      p.bytes += (size_t)d->c * p.Kp[i] * p.es;
+    }
+    if (k_order) p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->c) : p.C;
+  }
+  return p;
+}
+
+// Filter gradient: the kernel family, the column tile, the split of M into f32 slabs and the slabs' workspace.
+struct WgradPlan {
+  bool dma;                  // the LDS-DMA kernels (igemm_wgrad_dma_kernel, tdg_wgrad_patch.hip): large bf16 gradients
+  int bn;                    // column tile
+  int ntiles_k;              // K tiles of 256 (dma) or 128 rows
+  int nsplit, m_per_split;   // m_per_split is a multiple of the step's row count
+  size_t ws_bytes;
+};
+
+WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
+  WgradPlan p;
+  const int es = tdg_dtype_size(d->dtype), vec = 16 / es;
+  const int mr = d->dtype == TDG_BF16 ? WgGeom<bf16_t>::MR : WgGeom<float>::MR;
+  const int ce = eff_channels(d->c, d->cs, vec);
+  const long long KK = (long long)d->kh * d->kw * (ce ? ce : d->c);
+  const int bn = pick_bn(d->k);
+  // large bf16 filter gradients take the LDS-DMA kernel (256 x 208 tiles, one workgroup per CU)
+  const char* e = getenv("TDG_WDMA");                   // diagnostics: 0 disables
+  p.dma = false;
+  if (!(e && atoi(e) == 0) && d->dtype == TDG_BF16) {
+    static const int min_kk = getenv("TDG_WDMA_MINKK") ? atoi(getenv("TDG_WDMA_MINKK")) : 128;    // diagnostics
+    p.dma = ce != 0 && (bn == 208 || (bn == 128 && d->k > 112)) && KK >= min_kk;
+  }
+  // column tile: pick_bn's, except that the LDS-DMA kernel takes 256-column tiles for N % 256 == 0
+  // (pix2pix / VAE widths 256, 512, 1024: a third fewer operand bytes per MAC than 256 x 128)
+  static const int wide = getenv("TDG_WG256") ? atoi(getenv("TDG_WG256")) : 1;     // diagnostics: 0 = 128-column tiles
+  p.bn = wide && bn == 128 && p.dma && d->k % 256 == 0 ? 256 : bn;
+  p.ntiles_k = tdg_ceil_div(KK, p.dma ? 256 : 128);
+  const int M = n_images * d->oh * d->ow;
+  const int tiles = p.ntiles_k * tdg_ceil_div(d->k, p.bn);
+  int want = tdg_ceil_div(768, tiles);                  // register-staged kernel: ~3 workgroups per CU
+  if (p.dma) {
+    // one workgroup per CU: the fewest splits (each costs an f32 slab written and re-read) whose last round of
+    // 256 workgroups is within 10 % of the best fill any split count up to 16 (few tiles: up to 256 / tiles) reaches
+    static const int force = getenv("TDG_WSPLIT") ? atoi(getenv("TDG_WSPLIT")) : 0;   // diagnostics
+    double best = 0.0;
+    const int sp_max = tiles >= 16 ? 16 : 256 / tiles;    // few tiles: up to one round of splits
+    for (int sp = 1; sp <= sp_max; ++sp) {
+      const double fill = (double)tiles * sp / (256.0 * tdg_ceil_div((long long)tiles * sp, 256));
+      best = fill > best ? fill : best;
+    }
+    want = sp_max;
+    for (int sp = 1; sp <= sp_max; ++sp) {
+      const double fill = (double)tiles * sp / (256.0 * tdg_ceil_div((long long)tiles * sp, 256));
+      if (fill >= 0.9 * best) { want = sp; break; }
+    }
+    if (force) want = force;
+  }
+  const int max_split = tdg_ceil_div(M, mr * 4);        // keep >= 4 steps per split
+  if (want > max_split) want = max_split;
+  if (want < 1) want = 1;
+  if (want > 256) want = 256;
+  // 208-column LDS-DMA problems: splits of whole ring cycles (3 steps) of the patch-resident kernel, which runs its
+  // unrolled-by-stage loop to a multiple of 3 steps
+  const int unit = p.dma && p.bn == 208 ? 3 * mr : mr;
+  p.m_per_split = (int)tdg_round_up(tdg_ceil_div(M, want), unit);
+  p.nsplit = tdg_ceil_div(M, p.m_per_split);
+  p.ws_bytes = (size_t)p.nsplit * (size_t)tdg_round_up((long long)d->kh * d->kw * d->c * d->k, 4) * sizeof(float);
+  return p;
+}
+
+// The caller's epilogue into a kernel's argument block, for the fields that block has.  Also *col_nblk_out = 0: every
+// forward-type call writes it (include/tdg.h), and only a launch that grants column partials (grant_col_partial) raises it.
+template <class A, class = void> struct HasMask : std::false_type {};
+template <class A> struct HasMask<A, std::void_t<decltype(A::mask_mode)>> : std::true_type {};
+template <class A, class = void> struct HasAccumulate : std::false_type {};
+template <class A> struct HasAccumulate<A, std::void_t<decltype(A::accumulate)>> : std::true_type {};
+
+template <class A>
+void set_epilogue(A& f, const TdgEpilogue* e) {
+  f.bias = e ? e->bias : nullptr;
+  f.act = e ? e->act : TDG_ACT_NONE;
+  f.leak = e ? e->leak : 0.f;
+  if constexpr (HasMask<A>::value) {
+    f.mask_mode = e ? e->mask_mode : TDG_MASK_NONE;
+    f.mask_src = f.mask_mode != TDG_MASK_NONE ? static_cast<decltype(f.mask_src)>(e->mask_src) : nullptr;
+  }
+  if constexpr (HasAccumulate<A>::value) f.accumulate = e ? e->accumulate : 0;
+  if (e && e->col_nblk_out) *e->col_nblk_out = 0;
+}
+
+// an implicit-GEMM launch's arguments with the caller's epilogue and no split-K (launch_fwd_dma may split)
+IgArgs ig_args(const void* src, const void* wp, void* out, const TdgEpilogue* epi) {
+  IgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src;
+  a.wpack = wp;
+  a.out = out;
+  set_epilogue(a, epi);
+  a.ksplit = 1;
+  a.steps_per_split = 1 << 30;
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t tdg_packed_filter_fwd_bytes(const TdgConvDesc* d) {
   if (validate_desc(d, "tdg_packed_filter_fwd_bytes") != TDG_OK) return 0;
-  ThinPlan tp;
-  if (plan_fwd_thin(d, &tp)) return tp.w_bytes;
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  int ce = eff_channels(d->c, d->cs, vec);
-  if (!ce) ce = d->c;
-  const long long K = (long long)d->kh * d->kw * ce;
-  return (size_t)d->k * (size_t)tdg_round_up(K, bke) * es;
+  return plan_fwd(d, false).bytes;
 }
 
 size_t tdg_packed_filter_bwd_bytes(const TdgConvDesc* d) {
   if (validate_desc(d, "tdg_packed_filter_bwd_bytes") != TDG_OK) return 0;
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  int ke = eff_channels(d->k, d->ks, vec);
-  if (!ke) ke = d->k;
-  Col2imPlan cp;
-  if (plan_bwd_col2im(d, &cp)) return cp.w_bytes;
-  FusedPlan fp;
-  if (plan_bwd_fused(d, &fp)) return fp.w_bytes;
-  BwdClassPlan cls[IG_MAX_CLASSES];
-  const int nc = plan_bwd_classes(d, cls);
-  size_t total = 0;
-  for (int i = 0; i < nc; ++i) total += (size_t)d->c * (size_t)tdg_round_up((long long)cls[i].ntaps * ke, bke) * es;
-  return total;
+  return plan_bwd_data(d, false).bytes;
 }
 
 // ---- packing jobs ------------------------------------------------------------------------------------------------
-static void build_pack_fwd(const TdgConvDesc* d, const float* w, void* packed, PackArgs* a) {
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  int ce = eff_channels(d->c, d->cs, vec);
-  if (!ce) ce = d->c;
+static void build_pack_fwd(const TdgConvDesc* d, const FwdPlan& p, const float* w, void* packed, PackArgs* a) {
   a->w = w;
   a->out = packed;
   a->rows = d->k;
-  a->ntaps = d->kh * d->kw;
+  a->ntaps = p.ntaps;
   a->C = d->c;
-  a->Ceff = ce;
-  a->CK = (ce % vec == 0 && eff_channels(d->c, d->cs, vec)) ? k_slice_chunks(d->dtype, ce / vec, d->k) * vec : ce;
-  a->Kp = (int)tdg_round_up((long long)a->ntaps * ce, bke);
+  a->Ceff = p.C;
+  a->CK = p.veca ? p.ck * p.vec : p.ck;
+  a->Kp = p.Kp;
   a->stride_tap = d->c * d->k;
   a->stride_row = 1;       // row = small-side channel (last master index)
   a->stride_ch = d->k;     // K channel = big-side channel
-  int ord[IG_MAX_TAPS];
-  fwd_tap_order(d, ord);
-  for (int t = 0; t < a->ntaps; ++t) a->tap_ids[t] = (unsigned char)ord[t];
+  for (int t = 0; t < a->ntaps; ++t) a->tap_ids[t] = (unsigned char)p.ord[t];
   pack_finish(a);
 }
 
-// one job per non-empty parity class; returns the count (the fused-class form is not handled here)
-static int build_pack_bwd(const TdgConvDesc* d, const float* w, void* packed, PackArgs* out) {
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  int ke = eff_channels(d->k, d->ks, vec);
-  if (!ke) ke = d->k;
-  BwdClassPlan cls[IG_MAX_CLASSES];
-  const int nc = plan_bwd_classes(d, cls);
-  size_t off = 0;
+// one job per non-empty parity class of the class form; returns the count
+static int build_pack_bwd(const TdgConvDesc* d, const BwdDataPlan& p, const float* w, void* packed, PackArgs* out) {
   int n = 0;
-  for (int i = 0; i < nc; ++i) {
-    if (cls[i].ntaps == 0) continue;
+  for (int i = 0; i < p.nc; ++i) {
+    const BwdClassPlan& c = p.cls[i];
+    if (c.ntaps == 0) continue;
     PackArgs& a = out[n++];
     a.w = w;
-    a.out = static_cast<char*>(packed) + off;
+    a.out = static_cast<char*>(packed) + p.off[i];
     a.rows = d->c;
-    a.ntaps = cls[i].ntaps;
+    a.ntaps = c.ntaps;
     a.C = d->k;
-    a.Ceff = ke;
-    a.CK = (ke % vec == 0 && eff_channels(d->k, d->ks, vec)) ? k_slice_chunks(d->dtype, ke / vec, d->c) * vec : ke;
-    a.Kp = (int)tdg_round_up((long long)a.ntaps * ke, bke);
+    a.Ceff = p.C;
+    a.CK = p.veca ? p.ck * p.vec : p.ck;
+    a.Kp = p.Kp[i];
     a.stride_tap = d->c * d->k;
     a.stride_row = d->k;    // row = big-side channel
     a.stride_ch = 1;        // K channel = small-side channel (contiguous in the master)
-    for (int t = 0; t < a.ntaps; ++t) a.tap_ids[t] = (unsigned char)cls[i].tap_ids[t];
+    for (int t = 0; t < a.ntaps; ++t) a.tap_ids[t] = (unsigned char)c.tap_ids[t];
     pack_finish(&a);
-    off += (size_t)a.rows * a.Kp * es;
   }
   return n;
 }
@@ -4203,10 +4272,10 @@ int tdg_pack_filter_fwd(const TdgConvDesc* d, const float* w, void* packed, void
   int rc = validate_desc(d, "tdg_pack_filter_fwd");
   if (rc) return rc;
   TDG_CHECK_ARG(w && packed, "tdg_pack_filter_fwd: null pointer");
-  ThinPlan tp;
-  if (plan_fwd_thin(d, &tp)) return launch_pack_thin(d, tp, w, packed, (hipStream_t)stream);
+  const FwdPlan p = plan_fwd(d);
+  if (p.thin) return launch_pack_thin(d, p.tp, w, packed, (hipStream_t)stream);
   PackArgs a;
-  build_pack_fwd(d, w, packed, &a);
+  build_pack_fwd(d, p, w, packed, &a);
   return launch_pack_one(a, d->dtype, (hipStream_t)stream);
 }
 
@@ -4214,16 +4283,15 @@ int tdg_pack_filter_bwd(const TdgConvDesc* d, const float* w, void* packed, void
   int rc = validate_desc(d, "tdg_pack_filter_bwd");
   if (rc) return rc;
   TDG_CHECK_ARG(w && packed, "tdg_pack_filter_bwd: null pointer");
-  Col2imPlan cp;
-  if (plan_bwd_col2im(d, &cp)) {
+  const BwdDataPlan p = plan_bwd_data(d);
+  if (p.form == BWD_COL2IM) {
     PackArgs a;
-    build_pack_col2im(d, cp, w, packed, &a);
+    build_pack_col2im(d, p.cp, w, packed, &a);
     return launch_pack_one(a, d->dtype, (hipStream_t)stream);
   }
-  FusedPlan fp;
-  if (plan_bwd_fused(d, &fp)) return launch_pack_fused(d, fp, w, packed, (hipStream_t)stream);
+  if (p.form == BWD_FUSED) return launch_pack_fused(d, p.fp, w, packed, (hipStream_t)stream);
   PackArgs a[IG_MAX_CLASSES];
-  const int n = build_pack_bwd(d, w, packed, a);
+  const int n = build_pack_bwd(d, p, w, packed, a);
   for (int i = 0; i < n; ++i) {
     rc = launch_pack_one(a[i], d->dtype, (hipStream_t)stream);
     if (rc) return rc;
@@ -4267,41 +4335,40 @@ int tdg_pack_filters(const TdgPackJob* jobs, int n_jobs, void* stream) {
     TDG_CHECK_ARG(d->dtype == dtype, "tdg_pack_filters: job %d has dtype %d, job 0 has %d", j, d->dtype, dtype);
     TDG_CHECK_ARG(jobs[j].w, "tdg_pack_filters: job %d has no master filter", j);
     if (jobs[j].packed_fwd) {
-      ThinPlan tp;
-      if (plan_fwd_thin(d, &tp)) {
+      const FwdPlan p = plan_fwd(d);
+      if (p.thin) {
         if (m.thin_blocks == 0) {                              // rides in the multi-job launch (the first one of a call)
-          fill_pack_thin(d, tp, jobs[j].w, jobs[j].packed_fwd, &m.thin);
-          m.thin_blocks = tdg_ceil_div((long long)tp.rows * tp.WP, 256);
+          fill_pack_thin(d, p.tp, jobs[j].w, jobs[j].packed_fwd, &m.thin);
+          m.thin_blocks = tdg_ceil_div((long long)p.tp.rows * p.tp.WP, 256);
         } else {
-          rc = launch_pack_thin(d, tp, jobs[j].w, jobs[j].packed_fwd, (hipStream_t)stream);
+          rc = launch_pack_thin(d, p.tp, jobs[j].w, jobs[j].packed_fwd, (hipStream_t)stream);
           if (rc) return rc;
         }
       } else {
         PackArgs a;
-        build_pack_fwd(d, jobs[j].w, jobs[j].packed_fwd, &a);
+        build_pack_fwd(d, p, jobs[j].w, jobs[j].packed_fwd, &a);
         rc = push(a);
         if (rc) return rc;
       }
     }
     if (jobs[j].packed_bwd) {
-      FusedPlan fp;
-      Col2imPlan cp;
-      if (plan_bwd_col2im(d, &cp)) {
+      const BwdDataPlan p = plan_bwd_data(d);
+      if (p.form == BWD_COL2IM) {
         PackArgs a;
-        build_pack_col2im(d, cp, jobs[j].w, jobs[j].packed_bwd, &a);
+        build_pack_col2im(d, p.cp, jobs[j].w, jobs[j].packed_bwd, &a);
         rc = push(a);
         if (rc) return rc;
-      } else if (plan_bwd_fused(d, &fp)) {
+      } else if (p.form == BWD_FUSED) {
         if (m.fused_blocks == 0) {
-          fill_pack_fused(d, fp, jobs[j].w, jobs[j].packed_bwd, &m.fused);
-          m.fused_blocks = tdg_ceil_div(16 * fp.wpitch, 256);
+          fill_pack_fused(d, p.fp, jobs[j].w, jobs[j].packed_bwd, &m.fused);
+          m.fused_blocks = tdg_ceil_div(16 * p.fp.wpitch, 256);
         } else {
-          rc = launch_pack_fused(d, fp, jobs[j].w, jobs[j].packed_bwd, (hipStream_t)stream);
+          rc = launch_pack_fused(d, p.fp, jobs[j].w, jobs[j].packed_bwd, (hipStream_t)stream);
           if (rc) return rc;
         }
       } else {
         PackArgs a[IG_MAX_CLASSES];
-        const int n = build_pack_bwd(d, jobs[j].w, jobs[j].packed_bwd, a);
+        const int n = build_pack_bwd(d, p, jobs[j].w, jobs[j].packed_bwd, a);
         for (int i = 0; i < n; ++i) {
           rc = push(a[i]);
           if (rc) return rc;
@@ -4312,29 +4379,6 @@ int tdg_pack_filters(const TdgPackJob* jobs, int n_jobs, void* stream) {
   return flush();
 }
 
-static void fill_epilogue(IgArgs& a, const TdgEpilogue* epi) {
-  a.bias = epi ? epi->bias : nullptr;
-  a.act = epi ? epi->act : TDG_ACT_NONE;
-  a.leak = epi ? epi->leak : 0.f;
-  a.mask_mode = epi ? epi->mask_mode : TDG_MASK_NONE;
-  a.mask_src = epi ? epi->mask_src : nullptr;
-  a.accumulate = epi ? epi->accumulate : 0;
-  if (a.mask_mode == TDG_MASK_NONE) a.mask_src = nullptr;
-  // column partials: granted by launch_fwd_dma when the chosen kernel has the staged bf16 epilogue, else reported as 0 tiles
-  a.col_partial = nullptr;
-  a.col_mode = TDG_COL_NONE;
-  a.col_images = 0;
-  a.ksplit = 1;
-  a.steps_per_split = 1 << 30;
-  a.slab = nullptr;
-  t_splitk = (epi && epi->splitk_ws && epi->splitk_ws_bytes) ? epi : nullptr;
-  t_col = nullptr;
-  if (epi && epi->col_partial && epi->col_mode != TDG_COL_NONE && epi->col_nblk_out) {
-    *epi->col_nblk_out = 0;
-    t_col = epi;
-  }
-}
-
 int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void* wp, void* y,
                    const TdgEpilogue* epi, void* stream) {
   int rc = validate_desc(d, "tdg_conv2d_fwd");
@@ -4342,23 +4386,18 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
   TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_fwd: n_images %d outside (0, %d]", n_images, d->n);
   TDG_CHECK_ARG(x && wp && y, "tdg_conv2d_fwd: null pointer");
   TDG_CHECK_ARG(!epi || epi->mask_mode == TDG_MASK_NONE || epi->mask_src, "tdg_conv2d_fwd: mask without mask_src");
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  const int ce = eff_channels(d->c, d->cs, vec);
-  const bool veca = ce != 0;
-  const int C = veca ? ce : d->c;
-  TDG_CHECK_ARG(!veca || ((uintptr_t)x & 15) == 0, "tdg_conv2d_fwd: x must be 16-byte aligned (channel stride allows the vector gather)");
-  ThinPlan tp;
-  if (plan_fwd_thin(d, &tp) && !(epi && epi->accumulate)) {
+  const FwdPlan p = plan_fwd(d);
+  TDG_CHECK_ARG(!p.veca || ((uintptr_t)x & 15) == 0, "tdg_conv2d_fwd: x must be 16-byte aligned (channel stride allows the vector gather)");
+  const hipStream_t s = (hipStream_t)stream;
+  const double flops = conv_flops(d, n_images);
+  if (p.thin && !(epi && epi->accumulate)) {
+    const ThinPlan& tp = p.tp;
     ThinFwdArgs f;
     memset(&f, 0, sizeof(f));
     f.x = static_cast<const bf16_t*>(x);
     f.w = static_cast<const bf16_t*>(wp);
     f.y = static_cast<bf16_t*>(y);
-    f.bias = epi ? epi->bias : nullptr;
-    f.act = epi ? epi->act : TDG_ACT_NONE;
-    f.leak = epi ? epi->leak : 0.f;
-    f.mask_mode = epi ? epi->mask_mode : TDG_MASK_NONE;
-    f.mask_src = f.mask_mode != TDG_MASK_NONE ? static_cast<const bf16_t*>(epi->mask_src) : nullptr;
+    set_epilogue(f, epi);
     f.H = d->h; f.W = d->w; f.Cs = d->cs; f.C = d->c;
     f.OH = d->oh; f.OW = d->ow; f.Cso = d->ks; f.N = d->k;
     f.KH = d->kh; f.KW = d->kw; f.stride = d->stride; f.pad_t = d->pad_t; f.pad_l = d->pad_l;
@@ -4367,99 +4406,70 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
     f.fd_pw = make_fastdiv(tp.PW);
     f.fd_ow = make_fastdiv(d->ow);
     f.fd_c = make_fastdiv(d->c);
-    f.debug = 0;
 #ifdef TDG_STAMPS
     f.debug = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;     // (garbage results: diagnostic library only)
+    f.stamps = stamp_ptr();
 #endif
-    f.stamps = nullptr;
-#ifdef TDG_STAMPS
-    f.stamps = getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
-#endif
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_fwd_kernel<208>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&thin_fwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      attr_set = true;
-    }
-    const char* kname = tp.NC == 208 ? "thin_fwd_kernel<bf16>" : "thin_fwd_kernel<bf16,64>";
-    tdg_note_kernel(kname);
-    tdg_timing_start(kname, conv_flops(d, n_images), (hipStream_t)stream);
-    const dim3 tgrid(n_images * tp.tiles_per_image * tp.ntiles_n);
+    const dim3 grid(n_images * tp.tiles_per_image * tp.ntiles_n);
     if (tp.NC == 208)
-      hipLaunchKernelGGL(thin_fwd_kernel<208>, tgrid, dim3(256), tp.lds, (hipStream_t)stream, f);
-    else
-      hipLaunchKernelGGL(thin_fwd_kernel<64>, tgrid, dim3(256), tp.lds, (hipStream_t)stream, f);
-    tdg_timing_stop((hipStream_t)stream);
-    TDG_HIP_LAUNCH_CHECK("thin_fwd");
-    return TDG_OK;
+      return tdg_launch<thin_fwd_kernel<208>>("thin_fwd_kernel<bf16>", 80 * 1024, flops, s, [&] {
+        hipLaunchKernelGGL(thin_fwd_kernel<208>, grid, dim3(256), tp.lds, s, f);
+      });
+    return tdg_launch<thin_fwd_kernel<64>>("thin_fwd_kernel<bf16,64>", 80 * 1024, flops, s, [&] {
+      hipLaunchKernelGGL(thin_fwd_kernel<64>, grid, dim3(256), tp.lds, s, f);
+    });
   }
   static const int n1_enabled = getenv("TDG_CONVN1") ? atoi(getenv("TDG_CONVN1")) : 1;   // diagnostics: 0 = the 128 x 16 MFMA tile
-  if (n1_enabled && d->k == 1 && veca && k_slice_chunks(d->dtype, C / vec, d->k) == C / vec && d->kh * d->kw <= IG_MAX_TAPS && (long long)n_images * d->oh * d->ow >= 1024 &&
+  if (n1_enabled && d->k == 1 && p.veca && p.ck == p.C / p.vec && p.ntaps <= IG_MAX_TAPS && (long long)n_images * d->oh * d->ow >= 1024 &&
       !(epi && (epi->accumulate || epi->mask_mode != TDG_MASK_NONE))) {
-    if (epi && epi->col_nblk_out) *epi->col_nblk_out = 0;       // no column partials from this kernel: the host runs its own pass
-    ConvN1Args f;
+    ConvN1Args f;                                              // (no column partials from this kernel: the host runs its own pass)
     memset(&f, 0, sizeof(f));
     f.x = x; f.w = wp; f.y = y;
-    f.bias = epi ? epi->bias : nullptr;
-    f.act = epi ? epi->act : TDG_ACT_NONE;
-    f.leak = epi ? epi->leak : 0.f;
-    f.x_bytes = (unsigned)((long long)n_images * d->h * d->w * d->cs * es);
-    f.w_bytes = (unsigned)tdg_packed_filter_fwd_bytes(d);
-    f.SH = d->h; f.SW = d->w; f.Cs = d->cs; f.C = C; f.OH = d->oh; f.OW = d->ow; f.Cso = d->ks; f.stride = d->stride;
-    f.ntaps = d->kh * d->kw;
+    set_epilogue(f, epi);
+    f.x_bytes = (unsigned)((long long)n_images * d->h * d->w * d->cs * p.es);
+    f.w_bytes = (unsigned)p.bytes;
+    f.SH = d->h; f.SW = d->w; f.Cs = d->cs; f.C = p.C; f.OH = d->oh; f.OW = d->ow; f.Cso = d->ks; f.stride = d->stride;
+    f.ntaps = p.ntaps;
     f.M = n_images * d->oh * d->ow;
-    int ord[IG_MAX_TAPS];
-    fwd_tap_order(d, ord);
-    for (int t = 0; t < f.ntaps; ++t) f.tap[t] = pack_tap(ord[t] / d->kw - d->pad_t, ord[t] % d->kw - d->pad_l);
+    for (int t = 0; t < f.ntaps; ++t) f.tap[t] = pack_tap(p.ord[t] / d->kw - d->pad_t, p.ord[t] % d->kw - d->pad_l);
     f.fd_ohw = make_fastdiv(d->oh * d->ow);
     f.fd_ow = make_fastdiv(d->ow);
-    const char* name = d->dtype == TDG_BF16 ? "conv_n1_fwd_kernel<bf16>" : "conv_n1_fwd_kernel<f32>";
-    tdg_note_kernel(name);
-    tdg_timing_start(name, conv_flops(d, n_images), (hipStream_t)stream);
+    const dim3 grid(tdg_ceil_div(f.M, 4));
     if (d->dtype == TDG_BF16)
-      hipLaunchKernelGGL(conv_n1_fwd_kernel<bf16_t>, dim3(tdg_ceil_div(f.M, 4)), dim3(256), 0, (hipStream_t)stream, f);
-    else
-      hipLaunchKernelGGL(conv_n1_fwd_kernel<float>, dim3(tdg_ceil_div(f.M, 4)), dim3(256), 0, (hipStream_t)stream, f);
-    tdg_timing_stop((hipStream_t)stream);
-    TDG_HIP_LAUNCH_CHECK("conv_n1_fwd");
-    return TDG_OK;
+      return tdg_launch("conv_n1_fwd_kernel<bf16>", 0, flops, s, [&] {
+        hipLaunchKernelGGL(conv_n1_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, f);
+      });
+    return tdg_launch("conv_n1_fwd_kernel<f32>", 0, flops, s, [&] {
+      hipLaunchKernelGGL(conv_n1_fwd_kernel<float>, grid, dim3(256), 0, s, f);
+    });
   }
-  IgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src = x;
-  a.wpack = wp;
-  a.out = y;
-  fill_epilogue(a, epi);
-  a.src_bytes = (unsigned)((long long)n_images * d->h * d->w * d->cs * es);
-  a.w_bytes = (unsigned)tdg_packed_filter_fwd_bytes(d);
+  IgArgs a = ig_args(x, wp, y, epi);
+  a.src_bytes = (unsigned)((long long)n_images * d->h * d->w * d->cs * p.es);
+  a.w_bytes = (unsigned)p.bytes;
   a.SH = d->h; a.SW = d->w; a.sigma = d->stride;
-  a.C = C; a.Cs = d->cs;
-  a.fd_c = make_fastdiv(veca ? C / vec : C);
-  a.fd_ck = make_fastdiv(veca ? k_slice_chunks(d->dtype, C / vec, d->k) : C);
+  a.C = p.C; a.Cs = d->cs;
+  a.fd_c = make_fastdiv(p.veca ? p.C / p.vec : p.C);
+  a.fd_ck = make_fastdiv(p.ck);
   a.nslices = (int)(a.fd_c.d / a.fd_ck.d);
   a.N = d->k; a.OH = d->oh; a.OW = d->ow; a.os = 1; a.Cso = d->ks;
   a.nclasses = 1;
   IgClass& c = a.cls[0];
   c.M = n_images * d->oh * d->ow;
   c.GH = d->oh; c.GW = d->ow;
-  c.ntaps = d->kh * d->kw;
-  c.K = c.ntaps * C;
-  c.nsteps = tdg_ceil_div(c.K, bke);
-  c.Kp = c.nsteps * bke;
+  c.ntaps = p.ntaps;
+  c.K = c.ntaps * p.C;
+  c.Kp = p.Kp;
+  c.nsteps = p.Kp / p.bke;
   c.oh0 = c.ow0 = 0;
   c.w_off_bytes = 0;
   c.fd_ghw = make_fastdiv(c.GH * c.GW);
   c.fd_gw = make_fastdiv(c.GW);
-  int ord[IG_MAX_TAPS];
-  fwd_tap_order(d, ord);
-  for (int t = 0; t < c.ntaps; ++t) c.tap[t] = pack_tap(ord[t] / d->kw - d->pad_t, ord[t] % d->kw - d->pad_l);
+  for (int t = 0; t < c.ntaps; ++t) c.tap[t] = pack_tap(p.ord[t] / d->kw - d->pad_t, p.ord[t] % d->kw - d->pad_l);
   c.nh = d->kh; c.nw = d->kw; c.dh0 = -d->pad_t; c.dw0 = -d->pad_l; c.sh = c.sw = 1;
   c.fd_nw = make_fastdiv(c.nw);
   c.fd_nt = make_fastdiv(c.ntaps);
   const int bn = pick_bn(d->k);
-  t_flops = conv_flops(d, n_images);
-  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, veca, bn, (hipStream_t)stream)
-                              : launch_fwd<float>(a, veca, bn, (hipStream_t)stream);
+  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, p.veca, bn, flops, epi, s) : launch_fwd<float>(a, p.veca, bn, flops, epi, s);
 }
 
 int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const void* wp, void* x,
@@ -4469,71 +4479,54 @@ int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const
   TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_bwd_data: n_images %d outside (0, %d]", n_images, d->n);
   TDG_CHECK_ARG(x && wp && y, "tdg_conv2d_bwd_data: null pointer");
   TDG_CHECK_ARG(!epi || epi->mask_mode == TDG_MASK_NONE || epi->mask_src, "tdg_conv2d_bwd_data: mask without mask_src");
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es, bke = IG_BKB / es;
-  const int ke = eff_channels(d->k, d->ks, vec);
-  const bool veca = ke != 0;
-  const int C = veca ? ke : d->k;
-  TDG_CHECK_ARG(!veca || ((uintptr_t)y & 15) == 0, "tdg_conv2d_bwd_data: y must be 16-byte aligned (channel stride allows the vector gather)");
-  Col2imPlan cp;
-  if (plan_bwd_col2im(d, &cp)) {
+  const BwdDataPlan p = plan_bwd_data(d);
+  TDG_CHECK_ARG(!p.veca || ((uintptr_t)y & 15) == 0, "tdg_conv2d_bwd_data: y must be 16-byte aligned (channel stride allows the vector gather)");
+  const hipStream_t s = (hipStream_t)stream;
+  const double flops = conv_flops(d, n_images);
+  if (p.form == BWD_COL2IM) {
+    const Col2imPlan& cp = p.cp;
     Col2imArgs f;
     memset(&f, 0, sizeof(f));
     f.y = static_cast<const bf16_t*>(y);
     f.w = static_cast<const bf16_t*>(wp);
     f.x = static_cast<bf16_t*>(x);
-    f.bias = epi ? epi->bias : nullptr;
-    f.act = epi ? epi->act : TDG_ACT_NONE;
-    f.leak = epi ? epi->leak : 0.f;
-    f.mask_mode = epi ? epi->mask_mode : TDG_MASK_NONE;
-    f.mask_src = f.mask_mode != TDG_MASK_NONE ? static_cast<const bf16_t*>(epi->mask_src) : nullptr;
-    f.accumulate = epi ? epi->accumulate : 0;
+    set_epilogue(f, epi);
     f.SH = d->oh; f.SW = d->ow; f.Cs = d->ks;
     f.OH = d->h; f.OW = d->w; f.Cso = d->cs; f.C = d->c;
     f.KP = cp.KP; f.NT = cp.NT; f.pitch = cp.pitch; f.ke = cp.ke;
     f.TA = cp.TA; f.TW = cp.TW; f.ntr = cp.ntr; f.ntc = cp.ntc; f.HR = cp.HR; f.HC = cp.HC; f.dh_min = cp.dh_min; f.dw_min = cp.dw_min;
     f.p_off = cp.p_off;
-    f.debug = 0;
 #ifdef TDG_STAMPS
     f.debug = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;     // (garbage results: diagnostic library only)
 #endif
-    BwdClassPlan plan[IG_MAX_CLASSES];
-    plan_bwd_classes(d, plan);
     for (int i = 0; i < 4; ++i) {
-      const int ci = 2 * plan[i].oh0 + plan[i].ow0;
-      f.cls_ntaps[ci] = plan[i].ntaps;
-      for (int t = 0; t < plan[i].ntaps; ++t)
-        f.cls_tap[ci][t] = ((plan[i].dh[t] - cp.dh_min) << 16) | ((plan[i].dw[t] - cp.dw_min) << 8) | plan[i].tap_ids[t];
+      const BwdClassPlan& c = p.cls[i];
+      const int ci = 2 * c.oh0 + c.ow0;
+      f.cls_ntaps[ci] = c.ntaps;
+      for (int t = 0; t < c.ntaps; ++t) f.cls_tap[ci][t] = ((c.dh[t] - cp.dh_min) << 16) | ((c.dw[t] - cp.dw_min) << 8) | c.tap_ids[t];
     }
     f.fd_hc = make_fastdiv(cp.HC);
     f.fd_c = make_fastdiv(d->c);
     f.fd_ow2 = make_fastdiv(2 * cp.TW);
-    tdg_note_kernel("bwd_col2im_kernel<bf16>");
-    tdg_timing_start("bwd_col2im_kernel<bf16>", conv_flops(d, n_images), (hipStream_t)stream);
     const dim3 grid(n_images * cp.ntr * cp.ntc);
-    switch (cp.NT) {
-      case 1: hipLaunchKernelGGL(bwd_col2im_kernel<1>, grid, dim3(256), cp.lds, (hipStream_t)stream, f); break;
-      case 2: hipLaunchKernelGGL(bwd_col2im_kernel<2>, grid, dim3(256), cp.lds, (hipStream_t)stream, f); break;
-      case 3: hipLaunchKernelGGL(bwd_col2im_kernel<3>, grid, dim3(256), cp.lds, (hipStream_t)stream, f); break;
-      case 4: hipLaunchKernelGGL(bwd_col2im_kernel<4>, grid, dim3(256), cp.lds, (hipStream_t)stream, f); break;
-      default: hipLaunchKernelGGL(bwd_col2im_kernel<5>, grid, dim3(256), cp.lds, (hipStream_t)stream, f); break;
-    }
-    tdg_timing_stop((hipStream_t)stream);
-    TDG_HIP_LAUNCH_CHECK("bwd_col2im");
-    return TDG_OK;
+    return tdg_launch("bwd_col2im_kernel<bf16>", 0, flops, s, [&] {
+      switch (cp.NT) {
+        case 1: hipLaunchKernelGGL(bwd_col2im_kernel<1>, grid, dim3(256), cp.lds, s, f); break;
+        case 2: hipLaunchKernelGGL(bwd_col2im_kernel<2>, grid, dim3(256), cp.lds, s, f); break;
+        case 3: hipLaunchKernelGGL(bwd_col2im_kernel<3>, grid, dim3(256), cp.lds, s, f); break;
+        case 4: hipLaunchKernelGGL(bwd_col2im_kernel<4>, grid, dim3(256), cp.lds, s, f); break;
+        default: hipLaunchKernelGGL(bwd_col2im_kernel<5>, grid, dim3(256), cp.lds, s, f); break;
+      }
+    });
   }
-  FusedPlan fp;
-  if (plan_bwd_fused(d, &fp)) {
+  if (p.form == BWD_FUSED) {
+    const FusedPlan& fp = p.fp;
     FusedBwdArgs f;
     memset(&f, 0, sizeof(f));
     f.y = static_cast<const bf16_t*>(y);
     f.w = static_cast<const bf16_t*>(wp);
     f.x = static_cast<bf16_t*>(x);
-    f.bias = epi ? epi->bias : nullptr;
-    f.act = epi ? epi->act : TDG_ACT_NONE;
-    f.leak = epi ? epi->leak : 0.f;
-    f.mask_mode = epi ? epi->mask_mode : TDG_MASK_NONE;
-    f.mask_src = f.mask_mode != TDG_MASK_NONE ? static_cast<const bf16_t*>(epi->mask_src) : nullptr;
-    f.accumulate = epi ? epi->accumulate : 0;
+    set_epilogue(f, epi);
     f.SH = d->oh; f.SW = d->ow; f.Cs = d->ks; f.ke = fp.ke;
     f.OH = d->h; f.OW = d->w; f.Cso = d->cs; f.C = d->c;
     f.GH = fp.GH; f.GW = fp.GW;
@@ -4541,164 +4534,94 @@ int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const
     f.KP = fp.KP; f.PP = fp.PP; f.wpitch = fp.wpitch; f.TA = fp.TA; f.ntr = fp.ntr; f.TW = fp.TW; f.ntc = fp.ntc; f.y_off = fp.y_off;
     f.fd_vpp = make_fastdiv(fp.PP / 8);
     f.fd_hc = make_fastdiv(fp.TW + fp.nwm - 1);
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_set = true;
-    }
 #ifdef TDG_STAMPS
-    f.stamps = getenv("TDG_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("TDG_STAMP_PTR"), nullptr, 0) : nullptr;
+    f.stamps = stamp_ptr();
 #endif
-    tdg_note_kernel("bwd_fused_kernel<bf16>");
-    tdg_timing_start("bwd_fused_kernel<bf16>", conv_flops(d, n_images), (hipStream_t)stream);
-    hipLaunchKernelGGL(bwd_fused_kernel, dim3(n_images * fp.ntr * fp.ntc), dim3(512), fp.lds, (hipStream_t)stream, f);
-    tdg_timing_stop((hipStream_t)stream);
-    TDG_HIP_LAUNCH_CHECK("bwd_fused");
-    return TDG_OK;
+    return tdg_launch<bwd_fused_kernel>("bwd_fused_kernel<bf16>", 160 * 1024, flops, s, [&] {
+      hipLaunchKernelGGL(bwd_fused_kernel, dim3(n_images * fp.ntr * fp.ntc), dim3(512), fp.lds, s, f);
+    });
   }
-  IgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src = y;
-  a.wpack = wp;
-  a.out = x;
-  fill_epilogue(a, epi);
-  a.src_bytes = (unsigned)((long long)n_images * d->oh * d->ow * d->ks * es);
-  a.w_bytes = (unsigned)tdg_packed_filter_bwd_bytes(d);
+  IgArgs a = ig_args(y, wp, x, epi);
+  a.src_bytes = (unsigned)((long long)n_images * d->oh * d->ow * d->ks * p.es);
+  a.w_bytes = (unsigned)p.bytes;
   a.SH = d->oh; a.SW = d->ow; a.sigma = 1;
-  a.C = C; a.Cs = d->ks;
-  a.fd_c = make_fastdiv(veca ? C / vec : C);
-  a.fd_ck = make_fastdiv(veca ? k_slice_chunks(d->dtype, C / vec, d->c) : C);
+  a.C = p.C; a.Cs = d->ks;
+  a.fd_c = make_fastdiv(p.veca ? p.C / p.vec : p.C);
+  a.fd_ck = make_fastdiv(p.ck);
   a.nslices = (int)(a.fd_c.d / a.fd_ck.d);
   a.N = d->c; a.OH = d->h; a.OW = d->w; a.os = d->stride; a.Cso = d->cs;
-  BwdClassPlan plan[IG_MAX_CLASSES];
-  const int nc = plan_bwd_classes(d, plan);
-  a.nclasses = 0;
-  unsigned off = 0;
-  for (int i = 0; i < nc; ++i) {
-    const int Kp = (int)tdg_round_up((long long)plan[i].ntaps * C, bke);
-    if (plan[i].ntaps == 0 || plan[i].GH <= 0 || plan[i].GW <= 0) {
+  for (int i = 0; i < p.nc; ++i) {
+    const BwdClassPlan& pc = p.cls[i];
+    if (pc.ntaps == 0 || pc.GH <= 0 || pc.GW <= 0) {
       // a class without taps would leave its output pixels unwritten: only possible when the
       // filter is smaller than the stride, which the reference never uses
-      TDG_CHECK_ARG(plan[i].GH <= 0 || plan[i].GW <= 0, "tdg_conv2d_bwd_data: filter smaller than stride");
+      TDG_CHECK_ARG(pc.GH <= 0 || pc.GW <= 0, "tdg_conv2d_bwd_data: filter smaller than stride");
       continue;
     }
     IgClass& c = a.cls[a.nclasses++];
-    c.M = n_images * plan[i].GH * plan[i].GW;
-    c.GH = plan[i].GH; c.GW = plan[i].GW;
-    c.ntaps = plan[i].ntaps;
-    c.K = c.ntaps * C;
-    c.nsteps = tdg_ceil_div(c.K, bke);
-    c.Kp = Kp;
-    c.oh0 = plan[i].oh0; c.ow0 = plan[i].ow0;
-    c.w_off_bytes = off;
+    c.M = n_images * pc.GH * pc.GW;
+    c.GH = pc.GH; c.GW = pc.GW;
+    c.ntaps = pc.ntaps;
+    c.K = c.ntaps * p.C;
+    c.Kp = p.Kp[i];
+    c.nsteps = p.Kp[i] / p.bke;
+    c.oh0 = pc.oh0; c.ow0 = pc.ow0;
+    c.w_off_bytes = (unsigned)p.off[i];
     c.fd_ghw = make_fastdiv(c.GH * c.GW);
     c.fd_gw = make_fastdiv(c.GW);
-    for (int t = 0; t < c.ntaps; ++t) c.tap[t] = pack_tap(plan[i].dh[t], plan[i].dw[t]);
-    c.nh = plan[i].nh; c.nw = plan[i].nw; c.dh0 = plan[i].dh[0]; c.dw0 = plan[i].dw[0]; c.sh = c.sw = -1;
+    for (int t = 0; t < c.ntaps; ++t) c.tap[t] = pack_tap(pc.dh[t], pc.dw[t]);
+    c.nh = pc.nh; c.nw = pc.nw; c.dh0 = pc.dh[0]; c.dw0 = pc.dw[0]; c.sh = c.sw = -1;
     c.fd_nw = make_fastdiv(c.nw);
     c.fd_nt = make_fastdiv(c.ntaps);
-    off += (unsigned)((size_t)d->c * Kp * es);
   }
   const int bn = pick_bn(d->c);
-  t_flops = conv_flops(d, n_images);
-  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, veca, bn, (hipStream_t)stream)
-                              : launch_fwd<float>(a, veca, bn, (hipStream_t)stream);
-}
-
-// large bf16 filter gradients take the LDS-DMA kernel (256 x 208 tiles, one workgroup per CU)
-static bool wgrad_use_dma(const TdgConvDesc* d) {
-  const char* e = getenv("TDG_WDMA");                   // diagnostics: 0 disables
-  if (e && atoi(e) == 0) return false;
-  if (d->dtype != TDG_BF16) return false;
-  const int ce = eff_channels(d->c, d->cs, 8);
-  static const int min_kk = getenv("TDG_WDMA_MINKK") ? atoi(getenv("TDG_WDMA_MINKK")) : 128;    // diagnostics
-  const int bn = pick_bn(d->k);
-  return ce != 0 && (bn == 208 || (bn == 128 && d->k > 112)) && (long long)d->kh * d->kw * ce >= min_kk;
-}
-
-// column tile of the filter-gradient GEMM: pick_bn's, except that the LDS-DMA kernel takes 256-column tiles for N % 256 == 0
-// (pix2pix / VAE widths 256, 512, 1024: a third fewer operand bytes per MAC than 256 x 128)
-static int wgrad_bn(const TdgConvDesc* d) {
-  const int bn = pick_bn(d->k);
-  static const int wide = getenv("TDG_WG256") ? atoi(getenv("TDG_WG256")) : 1;     // diagnostics: 0 = 128-column tiles
-  if (wide && bn == 128 && wgrad_use_dma(d) && d->k % 256 == 0) return 256;
-  return bn;
-}
-
-static int wgrad_nsplit(const TdgConvDesc* d, int n_images, int* m_per_split) {
-  const int es = tdg_dtype_size(d->dtype), vec = 16 / es;
-  const int mr = d->dtype == TDG_BF16 ? WgGeom<bf16_t>::MR : WgGeom<float>::MR;
-  int ce = eff_channels(d->c, d->cs, vec);
-  if (!ce) ce = d->c;
-  const int M = n_images * d->oh * d->ow;
-  const bool dma = wgrad_use_dma(d);
-  const int tiles = tdg_ceil_div((long long)d->kh * d->kw * ce, dma ? 256 : 128) * tdg_ceil_div(d->k, wgrad_bn(d));
-  int want = tdg_ceil_div(768, tiles);                  // register-staged kernel: ~3 workgroups per CU
-  if (dma) {
-    // one workgroup per CU: the fewest splits (each costs an f32 slab written and re-read) whose last round of
-    // 256 workgroups is within 10 % of the best fill any split count up to 16 (few tiles: up to 256 / tiles) reaches
-    static const int force = getenv("TDG_WSPLIT") ? atoi(getenv("TDG_WSPLIT")) : 0;   // diagnostics
-    double best = 0.0;
-    const int sp_max = tiles >= 16 ? 16 : 256 / tiles;    // few tiles: up to one round of splits
-    for (int sp = 1; sp <= sp_max; ++sp) {
-      const double fill = (double)tiles * sp / (256.0 * tdg_ceil_div((long long)tiles * sp, 256));
-      best = fill > best ? fill : best;
-    }
-    want = sp_max;
-    for (int sp = 1; sp <= sp_max; ++sp) {
-      const double fill = (double)tiles * sp / (256.0 * tdg_ceil_div((long long)tiles * sp, 256));
-      if (fill >= 0.9 * best) { want = sp; break; }
-    }
-    if (force) want = force;
-  }
-  const int max_split = tdg_ceil_div(M, mr * 4);        // keep >= 4 steps per split
-  if (want > max_split) want = max_split;
-  if (want < 1) want = 1;
-  if (want > 256) want = 256;
-  // 208-column LDS-DMA problems: splits of whole ring cycles (3 steps) of the patch-resident kernel, which runs its
-  // unrolled-by-stage loop to a multiple of 3 steps
-  const int unit = dma && wgrad_bn(d) == 208 ? 3 * mr : mr;
-  int per = (int)tdg_round_up(tdg_ceil_div(M, want), unit);
-  *m_per_split = per;
-  return tdg_ceil_div(M, per);
+  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, p.veca, bn, flops, epi, s) : launch_fwd<float>(a, p.veca, bn, flops, epi, s);
 }
 
 size_t tdg_conv2d_bwd_filter_workspace_bytes(const TdgConvDesc* d, int n_images) {
   if (validate_desc(d, "tdg_conv2d_bwd_filter_workspace_bytes") != TDG_OK) return 0;
-  int per;
-  const int ns = wgrad_nsplit(d, n_images, &per);
-  return (size_t)ns * (size_t)tdg_round_up((long long)d->kh * d->kw * d->c * d->k, 4) * sizeof(float);
+  return plan_wgrad(d, n_images).ws_bytes;
 }
 
-static int bwd_filter_impl(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
-                           float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream);
+static int validate_wgrad(const TdgConvDesc* d, int n_images) {
+  int rc = validate_desc(d, "tdg_conv2d_bwd_filter");
+  if (rc) return rc;
+  TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_bwd_filter: n_images %d outside (0, %d]", n_images, d->n);
+  return TDG_OK;
+}
+
+static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_images, const void* x, int n_first, const void* x2,
+                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream);
 
 int tdg_conv2d_bwd_filter(const TdgConvDesc* d, int n_images, const void* x, const void* y, float* dw,
                           float beta, void* workspace, size_t workspace_bytes, void* stream) {
-  return bwd_filter_impl(d, n_images, x, n_images, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
+  const int rc = validate_wgrad(d, n_images);
+  if (rc) return rc;
+  return bwd_filter_impl(d, plan_wgrad(d, n_images), n_images, x, n_images, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
 }
 
 int tdg_conv2d_bwd_filter2(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
                            float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
   TDG_CHECK_ARG(n_first > 0 && n_first < n_images && x2, "tdg_conv2d_bwd_filter2: n_first %d outside (0, %d) or null x2", n_first, n_images);
+  int rc = validate_wgrad(d, n_images);
+  if (rc) return rc;
   // one launch when the LDS-DMA kernel applies and the switch row is even (a 2-row DMA instruction never straddles it)
-  if (wgrad_use_dma(d) && ((long long)n_first * d->oh * d->ow) % 2 == 0)
-    return bwd_filter_impl(d, n_images, x, n_first, x2, y, dw, beta, workspace, workspace_bytes, stream);
-  int rc = bwd_filter_impl(d, n_first, x, n_first, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
+  const WgradPlan p = plan_wgrad(d, n_images);
+  if (p.dma && ((long long)n_first * d->oh * d->ow) % 2 == 0)
+    return bwd_filter_impl(d, p, n_images, x, n_first, x2, y, dw, beta, workspace, workspace_bytes, stream);
+  rc = bwd_filter_impl(d, plan_wgrad(d, n_first), n_first, x, n_first, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
   if (rc) return rc;
   const char* y2 = static_cast<const char*>(y) + (size_t)n_first * d->oh * d->ow * d->ks * tdg_dtype_size(d->dtype);
-  return bwd_filter_impl(d, n_images - n_first, x2, n_images - n_first, nullptr, y2, dw, 1.0f, workspace, workspace_bytes, stream);
+  const int n2 = n_images - n_first;
+  return bwd_filter_impl(d, plan_wgrad(d, n2), n2, x2, n2, nullptr, y2, dw, 1.0f, workspace, workspace_bytes, stream);
 }
 
-static int bwd_filter_impl(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
-                           float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = validate_desc(d, "tdg_conv2d_bwd_filter");
-  if (rc) return rc;
-  TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_bwd_filter: n_images %d outside (0, %d]", n_images, d->n);
+// (d and n_images are validated; p = plan_wgrad(d, n_images))
+static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_images, const void* x, int n_first, const void* x2,
+                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
   TDG_CHECK_ARG(x && y && dw && workspace, "tdg_conv2d_bwd_filter: null pointer");
-  const size_t need = tdg_conv2d_bwd_filter_workspace_bytes(d, n_images);
-  if (workspace_bytes < need) {
-    tdg_set_error("tdg_conv2d_bwd_filter: workspace %zu < %zu bytes", workspace_bytes, need);
+  if (workspace_bytes < p.ws_bytes) {
+    tdg_set_error("tdg_conv2d_bwd_filter: workspace %zu < %zu bytes", workspace_bytes, p.ws_bytes);
     return TDG_EWORKSPACE;
   }
   const int es = tdg_dtype_size(d->dtype), vec = 16 / es;
@@ -4730,15 +4653,15 @@ static int bwd_filter_impl(const TdgConvDesc* d, int n_images, const void* x, in
   a.N = (int)tdg_round_up(d->k, vec) <= d->ks ? (int)tdg_round_up(d->k, vec) : d->k;
   a.Gs = d->ks;
   a.Nlog = d->k;
-  a.nsplit = wgrad_nsplit(d, n_images, &a.m_per_split);
+  a.nsplit = p.nsplit;
+  a.m_per_split = p.m_per_split;
   a.slab_stride = tdg_round_up((long long)a.ntaps * d->c * d->k, 4);
-  const int bn = wgrad_bn(d);
-  const bool dma = wgrad_use_dma(d);
-  a.ntiles_n = tdg_ceil_div(a.N, bn);
-  a.ntiles_k = tdg_ceil_div(a.KK, dma ? 256 : 128);
+  a.ntiles_n = tdg_ceil_div(a.N, p.bn);
+  a.ntiles_k = p.ntiles_k;
   for (int kh = 0; kh < d->kh; ++kh)
     for (int kw = 0; kw < d->kw; ++kw) a.tap[kh * d->kw + kw] = pack_tap(kh - d->pad_t, kw - d->pad_l);
-  t_flops = conv_flops(d, n_images);
+  const hipStream_t s = (hipStream_t)stream;
+  const double flops = conv_flops(d, n_images);
   // loader mode of the gathered operand (WdLoader): 1 = a 64-row step of whole images, 2 = a rectangle of one image
   // (whole grid rows, or a 64-column piece of one), 0 = anything else.  TDG_WDMA_SLOWA (diagnostics) forces 0.
   const int ghw = d->oh * d->ow;
@@ -4749,38 +4672,34 @@ static int bwd_filter_impl(const TdgConvDesc* d, int n_images, const void* x, in
   if (getenv("TDG_WDMA_SLOWA")) mode = 0;
   auto go = [&](auto bn_c) -> int {
     constexpr int B = decltype(bn_c)::value;
-    return mode == 1 ? launch_wgrad_dma<B, 1>(a, (hipStream_t)stream)
-                     : (mode == 2 ? launch_wgrad_dma<B, 2>(a, (hipStream_t)stream) : launch_wgrad_dma<B, 0>(a, (hipStream_t)stream));
+    return mode == 1 ? launch_wgrad_dma<B, 1>(a, flops, s) : (mode == 2 ? launch_wgrad_dma<B, 2>(a, flops, s) : launch_wgrad_dma<B, 0>(a, flops, s));
   };
   // whole-image steps of a 208-column problem: the patch-resident kernel (tdg_wgrad_patch.hip) where its plan applies.
   // TDG_WPATCH=0 (variant tests) keeps the slab kernel.
+  int rc = TDG_OK;
   bool patched = false;
-  if (dma && bn == 208 && mode == 1 && !(getenv("TDG_WPATCH") && atoi(getenv("TDG_WPATCH")) == 0)) {
+  if (p.dma && p.bn == 208 && mode == 1 && !(getenv("TDG_WPATCH") && atoi(getenv("TDG_WPATCH")) == 0)) {
     WpPlan wp;
     if (tdg_wgrad_patch_plan(a, &wp)) {
-      rc = tdg_wgrad_patch_launch(a, wp, t_flops, (hipStream_t)stream);
+      rc = tdg_wgrad_patch_launch(a, wp, flops, s);
       if (rc) return rc;
       patched = true;
     }
   }
   if (!patched)
-  rc = dma ? (bn == 208 ? go(std::integral_constant<int, 208>{}) : bn == 256 ? go(std::integral_constant<int, 256>{}) : go(std::integral_constant<int, 128>{}))
-           : d->dtype == TDG_BF16 ? launch_wgrad<bf16_t>(a, veca, bn, (hipStream_t)stream)
-                                  : launch_wgrad<float>(a, veca, bn, (hipStream_t)stream);
+    rc = p.dma ? (p.bn == 208 ? go(IntC<208>{}) : p.bn == 256 ? go(IntC<256>{}) : go(IntC<128>{}))
+               : d->dtype == TDG_BF16 ? launch_wgrad<bf16_t>(a, veca, p.bn, flops, s) : launch_wgrad<float>(a, veca, p.bn, flops, s);
   if (rc) return rc;
   const size_t n = (size_t)a.ntaps * d->c * d->k;
-  tdg_timing_start("slab_reduce", 0.0, (hipStream_t)stream);
-  if (a.nsplit <= 8 && ((uintptr_t)dw & 15) == 0) {
-    hipLaunchKernelGGL(slab_reduce_few_kernel, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a.slabs,
-                       dw, n, a.nsplit, (size_t)a.slab_stride, beta);
-  } else {
-    const int blocks = (int)(((n + 3) / 4 + 15) / 16);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a.slabs, dw, n, a.nsplit,
-                       (size_t)a.slab_stride, beta);
-  }
-  tdg_timing_stop((hipStream_t)stream);
-  TDG_HIP_LAUNCH_CHECK("slab_reduce");
-  return TDG_OK;
+  return tdg_launch("slab_reduce", 0, 0.0, s, [&] {
+    if (a.nsplit <= 8 && ((uintptr_t)dw & 15) == 0) {
+      hipLaunchKernelGGL(slab_reduce_few_kernel, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, s, a.slabs, dw, n, a.nsplit,
+                         (size_t)a.slab_stride, beta);
+    } else {
+      const int blocks = (int)(((n + 3) / 4 + 15) / 16);
+      hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slabs, dw, n, a.nsplit, (size_t)a.slab_stride, beta);
+    }
+  }, false);                                                   // (tdg_last_kernel keeps the GEMM's name)
 }
 
 }  // extern "C"

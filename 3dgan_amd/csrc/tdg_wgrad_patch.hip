@@ -489,21 +489,12 @@ static bool wp_plan_search(const WgArgs& a, WpPlan* p) {
 template <int NW, int NSLOT>
 static int wp_launch(WgArgs& a, WpPlan& p, double flops, hipStream_t s) {
   const size_t lds = WP_LDS + IG_MAX_TAPS * sizeof(int);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_patch_kernel<NW, NSLOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  static char name[64] = "";
-  if (!name[0]) snprintf(name, sizeof(name), "igemm_wgrad_patch_kernel<bf16,256,208,%d,%d>", NW, NSLOT);
   p.nslot = NSLOT;
-  dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(64 * NW);
-  tdg_note_kernel(name);
-  tdg_timing_start(name, flops, s);
-  hipLaunchKernelGGL((igemm_wgrad_patch_kernel<NW, NSLOT>), grid, block, lds, s, a, p);
-  tdg_timing_stop(s);
-  TDG_HIP_LAUNCH_CHECK("igemm_wgrad_patch");
-  return TDG_OK;
+  const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(64 * NW);
+  const char* name = TDG_NAME("igemm_wgrad_patch_kernel<bf16,256,208,%d,%d>", NW, NSLOT);
+  return tdg_launch<igemm_wgrad_patch_kernel<NW, NSLOT>>(name, (int)lds, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_wgrad_patch_kernel<NW, NSLOT>), grid, block, lds, s, a, p);
+  });
 }
 
 int tdg_wgrad_patch_launch(WgArgs& a, WpPlan& p, double flops, hipStream_t s) {

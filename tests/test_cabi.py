@@ -41,6 +41,29 @@ def test_argument_errors_are_reported_not_thrown():
     assert lib.tdg_conv2d_bwd_filter_workspace_bytes(C.byref(d), 2) >= 25 * 8 * 16 * 4
 
 
+def test_sizes_of_each_conv_form():
+    """Packed filter and filter-gradient workspace sizes of one descriptor per form (values of the implementation before
+    the sizing, packing and launch code shared one plan per direction)."""
+    import ctypes as C
+    L = pkg('_lib')
+    lib = L.load()
+    cases = [  # (n, h, w, c, cs, oh, ow, k, ks, kh, kw, stride, pad_t, pad_l, dtype): fwd, bwd, workspace (n, n // 2 images)
+        ((64, 64, 64, 3, 4, 32, 32, 200, 200, 5, 5, 2, 1, 1, 1), (46592, 64768, 15360000, 7680000)),           # thin / fused
+        ((64, 8, 8, 400, 400, 4, 4, 800, 800, 5, 5, 2, 1, 1, 1), (16076800, 16025600, 96000000, 64000000)),   # 5-chunk K slices
+        ((16, 64, 64, 2, 2, 32, 32, 64, 64, 4, 4, 2, 1, 1, 1), (8192, 4096, 524288, 262144)),                 # scalar gather / col2im
+        ((16, 64, 64, 3, 4, 32, 32, 16, 16, 4, 4, 2, 1, 1, 1), (2048, 3072, 196608, 98304)),                  # col2im
+        ((16, 32, 32, 64, 64, 16, 16, 128, 128, 4, 4, 2, 1, 1, 1), (262144, 262144, 8388608, 4194304)),       # parity classes
+        ((16, 32, 32, 50, 50, 16, 16, 100, 100, 5, 5, 2, 2, 2, 1), (256000, 268800, 8000000, 4000000)),       # compact strides
+        ((2, 8, 8, 8, 8, 4, 4, 16, 16, 5, 5, 2, 1, 1, 0), (14336, 13312, 12800, 12800)),                       # f32
+    ]
+    for t, want in cases:
+        d = L.ConvDesc(*t)
+        got = (lib.tdg_packed_filter_fwd_bytes(C.byref(d)), lib.tdg_packed_filter_bwd_bytes(C.byref(d)),
+               lib.tdg_conv2d_bwd_filter_workspace_bytes(C.byref(d), t[0]),
+               lib.tdg_conv2d_bwd_filter_workspace_bytes(C.byref(d), t[0] // 2))
+        assert got == want, (t, got, want)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     L = pkg('_lib')
     import pytest
