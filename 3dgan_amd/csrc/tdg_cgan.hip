@@ -1,7 +1,7 @@
 // paper_cgan pieces that are not GEMMs (hem/models/paper_cgan.py): the depth target's crop / rescale / per-image mean,
 // the 1x1 one-output-channel generator head with its top-left crop, the D input join of the shared rgb path, the WGAN
 // loss on sigmoid outputs and the Eigen-2014 depth metrics.  All of them are memory-bound; wave64 throughout.
-#include "tdg_common.h"
+#include "tdg_cgan_metrics.h"
 
 #define DISPATCH_T(dtype, ...)                  \
   if ((dtype) == TDG_BF16) {                    \
@@ -18,7 +18,6 @@
 namespace {
 
 constexpr int kSrc = 65, kCrop = 29, kOff = 17;          // paper_cgan.py:93-94: crop_to_bounding_box(y * 10, 17, 17, 29, 29)
-constexpr int kMetricBlocks = 256;
 
 inline int grid_for(size_t n) {
   const size_t b = (n + 255) / 256;
@@ -26,11 +25,6 @@ inline int grid_for(size_t n) {
 }
 
 __device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wsum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
@@ -255,14 +249,7 @@ __global__ void __launch_bounds__(256) cgan_wgan_kernel(const T* __restrict__ z,
   }
 }
 
-// ---- Eigen-2014 metrics (paper_cgan.py:447-478) --------------------------------------------------------------------
-// per element (a = y / 10, p = pred / 10): |a-p|/p, (a-p)^2/p, (a-p)^2, d^2, d with d = log(a+1e-8) - log(p+1e-8);
-// threshold hits: max(a/p, p/a) < 1.25^k with tf.maximum's NaN rule (x < y ? y : x)
-struct MetricPartial {
-  double s[5];
-  unsigned long long hits[3];
-};
-
+// ---- Eigen-2014 metrics (paper_cgan.py:447-478): the terms, the reduction and the values are tdg_cgan_metrics.h's ----
 __global__ void __launch_bounds__(256) cgan_metrics_kernel(const float* __restrict__ y, const float* __restrict__ pred,
                                                            const float* __restrict__ offset, int n, int hw,
                                                            MetricPartial* __restrict__ part) {
@@ -273,63 +260,19 @@ __global__ void __launch_bounds__(256) cgan_metrics_kernel(const float* __restri
   const size_t total = (size_t)n * hw;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int b = (int)(i / hw);
-    const float a = y[i] / 10.f;
-    const float p = ((pred ? pred[i] : 0.f) + (offset ? offset[b] : 0.f)) / 10.f;
-    const float e = a - p;
-    const float d = logf(a + 1e-8f) - logf(p + 1e-8f);
-    s[0] += (double)(fabsf(e) / p);
-    s[1] += (double)(e * e / p);
-    s[2] += (double)(e * e);
-    s[3] += (double)(d * d);
-    s[4] += (double)d;
-    const float q1 = a / p, q2 = p / a;
-    const float delta = q1 < q2 ? q2 : q1;
-    h[0] += delta < 1.25f;
-    h[1] += delta < 1.5625f;
-    h[2] += delta < 1.953125f;
+    metric_terms(y[i], (pred ? pred[i] : 0.f) + (offset ? offset[b] : 0.f), s, h);
   }
-  const int wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const double v = wsum_d(s[k]);
-    if ((threadIdx.x & 63) == 0) shd[k][wv] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    unsigned long long v = h[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) shh[k][wv] = v;
-  }
+  metric_wave_sums(s, h, shd, shh);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    MetricPartial m;
-    for (int k = 0; k < 5; ++k) m.s[k] = shd[k][0] + shd[k][1] + shd[k][2] + shd[k][3];
-    for (int k = 0; k < 3; ++k) m.hits[k] = shh[k][0] + shh[k][1] + shh[k][2] + shh[k][3];
-    part[blockIdx.x] = m;
-  }
+  if (threadIdx.x == 0) part[blockIdx.x] = metric_block_total(shd, shh);
 }
 
 __global__ void cgan_metrics_finish_kernel(const MetricPartial* __restrict__ part, int nblk, unsigned long long total,
                                            unsigned long long* __restrict__ counts, float* __restrict__ out) {
   if (threadIdx.x != 0) return;
-  double s[5] = {0, 0, 0, 0, 0};
-  unsigned long long h[3] = {0, 0, 0};
-  for (int b = 0; b < nblk; ++b) {
-    for (int k = 0; k < 5; ++k) s[k] += part[b].s[k];
-    for (int k = 0; k < 3; ++k) h[k] += part[b].hits[k];
-  }
-  const double n = (double)total;
-  out[0] = (float)(s[0] / n);
-  out[1] = (float)(s[1] / n);
-  out[2] = (float)sqrt(s[2] / n);
-  out[3] = (float)sqrt(s[3] / n);
-  out[4] = (float)(s[3] / n - s[4] * s[4] / (n * n));
-  counts[3] += total;
-  for (int k = 0; k < 3; ++k) {
-    counts[k] += h[k];
-    out[5 + k] = (float)((double)counts[k] / (double)counts[3]);
-  }
+  double v[8];
+  metric_values(part, nblk, total, counts, v);
+  for (int k = 0; k < 8; ++k) out[k] = (float)v[k];
 }
 
 }  // namespace
@@ -439,8 +382,7 @@ extern "C" int tdg_cgan_metrics(const float* y, const float* pred, const float* 
     return TDG_EWORKSPACE;
   }
   const size_t total = (size_t)n * hw;
-  int nblk = (int)((total + 1023) / 1024);
-  nblk = nblk < 1 ? 1 : (nblk > kMetricBlocks ? kMetricBlocks : nblk);
+  const int nblk = metric_blocks(total);
   MetricPartial* part = static_cast<MetricPartial*>(workspace);
   tdg_timing_start("cgan_metrics", 0.0, (hipStream_t)stream);
   hipLaunchKernelGGL(cgan_metrics_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, y, pred, offset, n, hw, part);

@@ -143,11 +143,12 @@ class NYUv2Dataset(DataPlugin):
         return rgb, depth
 
     @staticmethod
-    def get_source(args, sess):
+    def get_source(args, sess, split='train'):
+        """`split`: which records feed the source (paper_metrics.py opens `validate` too)."""
         for flag in ('include_location', 'normalize', 'include_originals'):
             if getattr(args, flag, None):
                 sys.stderr.write('WARNING: --%s only feeds the thesis samplers; ignored\n' % flag)
-        rgb, depth = NYUv2Dataset.load(args)
+        rgb, depth = NYUv2Dataset.load(args, split)
         crop = tuple(args.random_crop) if getattr(args, 'random_crop', None) else None
         seed = args.seed if isinstance(getattr(args, 'seed', None), int) else 0
         src = PairSource(rgb, depth, args.batch_size, sess.device, crop, getattr(args, 'resize', None), seed, sess.rank,

@@ -20,6 +20,10 @@ Reference-effective behaviour and what is opt-in:
     both D and G variables are clamped to [-c, c] before their steps.
   * the threshold metrics are tf.metrics.percentage_below: running totals since the model was built, never reset.
 
+Dataset evaluation (paper/paper_metrics.py, the mean / variance image pre-pass of paper/paper_train.py:43-60,130-132 and
+`metrics_y_mean`, :79,177): set_mean_image / dataset_moments / evaluate on the kernels of tdg_cgan_eval.hip; a sweep adds
+every batch into device-resident f64 accumulators and reads the host once.
+
 MI355X-native: activations are NHWC; the generator's skip concats are zero-copy channel windows (as models/pix2pix.py);
 D's rgb path runs ONCE over the B images -- it is identical for D(x, y) and D(x, y_hat) -- and its output fills the left
 window of both halves of the combined input (tdg_cgan_join), its backward sums the two halves' gradients first; the depth
@@ -201,6 +205,17 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         self.metric_out = f32(8)
         self.metric_ws = torch.zeros(_lib.load().tdg_cgan_metrics_workspace_bytes(), dtype=torch.uint8, device=dev)
         self._full = {}                                      # infer_full's frame buffers by (H, W, stride)
+        # dataset evaluation (tdg_cgan_eval.hip): the mean image of metrics_y_mean with its own streaming totals (row 2 of
+        # [set, 4]), and evaluate()'s accumulators, totals and results
+        lib = _lib.load()
+        f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+        self.mean_image = None
+        self.mean_counts = torch.zeros(3, 4, dtype=torch.int64, device=dev)
+        self.eval_acc = f64(lib.tdg_cgan_eval_acc_bytes(CROP * CROP) // 8)
+        self.eval_counts = torch.zeros(3, 4, dtype=torch.int64, device=dev)
+        self.eval_scalars = f64(3, 12)
+        self.eval_mean, self.eval_var = f32(CROP, CROP), f32(CROP, CROP)
+        self.eval_ws = torch.zeros(lib.tdg_cgan_eval_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.init_graphs(args, sess)
         self.refresh()
 
@@ -251,9 +266,13 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         B, dt = self.B, self.sess.dtype
         rows = B * SRC * SRC
         _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.Dr.x.cs, 1.0, 0.0, self.Dr.x.ptr(0), K.stream())
-        mp2 = self.version == 2
-        if mp2:
+        if self.version == 2:
             _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.gx.cs, 1.0, 0.0, self.gx.ptr(0), K.stream())
+        self._target(ybar, crop)
+
+    def _target(self, ybar, crop):
+        """The depth half of _inputs: the staged y into the depth target, y_bar and the f32 crop."""
+        B, dt, mp2 = self.B, self.sess.dtype, self.version == 2
         _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage), B, self.version, self.Dd.x.ptr(0), self.Dd.x.cs,
                   self.Dd.x.ptr(B) if mp2 else None, K.ptr(ybar), K.ptr(crop),
                   self.gx.window(3, 1).ptr(0) if mp2 else None, self.gx.cs,
@@ -368,6 +387,95 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
             _lib.call('tdg_cgan_metrics', K.ptr(self.crop), K.ptr(pred), K.ptr(off), self.B, CROP * CROP, K.ptr(self.counts[name]),
                       K.ptr(self.metric_out), K.ptr(self.metric_ws), self.metric_ws.numel(), K.stream())
             out['metrics_' + name] = dict(zip(METRIC_KEYS, self.metric_out.cpu().tolist()))
+        if self.mean_image is not None:                          # metrics_y_mean (:79, :177): 10 * mean image, no y_bar added
+            self.eval_acc.zero_()
+            self._eval_batch(self.crop, None, None, self.mean_image, 4, self.mean_counts)
+            out['metrics_y_mean'] = dict(zip(METRIC_KEYS, self.eval_acc[18:26].float().cpu().tolist()))
+        return out
+
+    def set_mean_image(self, img01):
+        """The reference's mean_image_placeholder: a [29,29] or [1,29,29] depth image in [0, 1] (dataset_moments' mean), kept
+        on the device; while one is set, metrics() also reports `metrics_y_mean`.  None clears it."""
+        if img01 is None:
+            self.mean_image = None
+            return
+        img = torch.as_tensor(img01).to(device=self.sess.device, dtype=torch.float32)
+        if tuple(img.shape) not in ((CROP, CROP), (1, CROP, CROP)):
+            raise ValueError('set_mean_image: expected [%d,%d] or [1,%d,%d], got %s' % (CROP, CROP, CROP, CROP, tuple(img.shape)))
+        self.mean_image = img.reshape(CROP, CROP).contiguous().clone()
+
+    def _eval_batch(self, crop, yhat, y_0, image01, sets, counts):
+        """tdg_cgan_eval_batch of one batch into self.eval_acc: sets 1 (yhat), 2 (y_0, None: zero), 4 (10 * image01)."""
+        _lib.call('tdg_cgan_eval_batch', K.ptr(crop), K.ptr(yhat), K.ptr(y_0), K.ptr(image01), 10.0, self.B, CROP * CROP, sets,
+                  K.ptr(counts), K.ptr(self.eval_acc), K.ptr(self.eval_ws), self.eval_ws.numel(), K.stream())
+
+    def _eval_finish(self, images):
+        _lib.call('tdg_cgan_eval_finish', K.ptr(self.eval_acc), K.ptr(self.eval_counts), CROP * CROP, 10.0, K.ptr(self.eval_scalars),
+                  K.ptr(self.eval_mean) if images else None, K.ptr(self.eval_var) if images else None, K.stream())
+
+    def _eval_sweep(self, source, n_batches, name, body, both=True):
+        """`body` once per batch of `source`, graph-replayed, on the batch staged at fixed addresses."""
+        for _ in range(n_batches):
+            batch = source.next_batch()
+            if both:
+                self._stage(batch)
+            else:
+                self.y_stage.copy_(batch[1].reshape(self.y_stage.shape))
+            self._run(name, body)
+
+    def _eval_model_body(self):
+        """Sweep 1: infer()'s path, then y_hat, y_0 and the moments from one read of the crop."""
+        self._inputs(self.inf_ybar, self.inf_crop)
+        self._generate(self.inf_ybar, self.inf_yhat)
+        self._eval_batch(self.inf_crop, self.inf_yhat, self.inf_ybar if self.version != 0 else None, None, 3, self.eval_counts)
+        self._moments_body(prep=False)
+
+    def _eval_mean_body(self):
+        """Sweep 2: no generator pass; the mean image of sweep 1 against this batch's crop."""
+        self._target(self.inf_ybar, self.inf_crop)
+        self._eval_batch(self.inf_crop, None, None, self.eval_mean, 4, self.eval_counts)
+
+    def _moments_body(self, prep=True):
+        if prep:
+            self._target(self.inf_ybar, self.inf_crop)
+        _lib.call('tdg_cgan_eval_moments', K.ptr(self.inf_crop), self.B, CROP * CROP, K.ptr(self.eval_acc), K.stream())
+
+    @staticmethod
+    def _check_sweep(what, n_batches):
+        if int(n_batches) < 1:
+            raise ValueError('%s: n_batches must be at least 1, got %r' % (what, n_batches))
+        return int(n_batches)
+
+    def dataset_moments(self, source, n_batches):
+        """(mean_img, var_img), NumPy f32 [29,29]: tf.nn.moments over the batch axis of the [0, 1] depth crop of each of
+        `n_batches` batches of `source`, averaged over the batches (paper_train.py:43-50, :130-132)."""
+        n_batches = self._check_sweep('dataset_moments', n_batches)
+        self.eval_acc.zero_()
+        self._eval_sweep(source, n_batches, 'eval_moments', self._moments_body, both=False)
+        self._eval_finish(True)
+        return self.eval_mean.cpu().numpy(), self.eval_var.cpu().numpy()
+
+    def evaluate(self, source, n_batches):
+        """paper_metrics.py's calculate_metrics over `n_batches` batches of `source`, twice: sweep 1 evaluates the model's
+        y_hat (`model`) and y_0 = 0 / y_bar (`zero`) and takes the moments; sweep 2, on the next n_batches batches, evaluates
+        the mean image of sweep 1 (`mean`).  Each set: METRIC_KEYS averaged over the batches (thresholds: the mean of the
+        running percentage, :24-34,119-130) plus `threshold{1,2,3}_final`, the totals' percentages; the totals start at zero
+        in every call.  Also `mean_image` / `var_image` (NumPy f32 [29,29], [0, 1] units), `n_batches`, `images`.
+        One host read; training state, metrics() and its buffers are untouched."""
+        n_batches = self._check_sweep('evaluate', n_batches)
+        self.eval_acc.zero_()
+        self.eval_counts.zero_()
+        self._eval_sweep(source, n_batches, 'eval_model', self._eval_model_body)
+        self._eval_finish(True)
+        self._eval_sweep(source, n_batches, 'eval_mean', self._eval_mean_body, both=False)
+        self._eval_finish(False)
+        rows = self.eval_scalars.cpu().tolist()
+        out = {}
+        for name, r in zip(('model', 'zero', 'mean'), rows):
+            out[name] = dict(zip(METRIC_KEYS, r[:8]))
+            out[name].update({'threshold%d_final' % (k + 1): r[8 + k] for k in range(3)})
+        out.update(mean_image=self.eval_mean.cpu().numpy(), var_image=self.eval_var.cpu().numpy(), n_batches=n_batches,
+                   images=n_batches * self.B)
         return out
 
     def infer(self, batch):

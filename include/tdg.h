@@ -315,6 +315,30 @@ int tdg_cgan_wgan_loss(int dtype, const void* logits, int rows, int cs, int mode
 int tdg_cgan_metrics(const float* y, const float* pred, const float* offset, int n, int hw, unsigned long long* counts, float* out,
                      void* workspace, size_t workspace_bytes, void* stream);
 size_t tdg_cgan_metrics_workspace_bytes(void);
+/* ---- paper_cgan dataset evaluation (paper/paper_metrics.py, paper/paper_train.py:43-60; 3dgan_amd/csrc/tdg_cgan_eval.hip) --
+ * A sweep over a split adds every batch into device-resident accumulators and reads the host once, after tdg_cgan_eval_finish.
+ * acc: tdg_cgan_eval_acc_bytes(hw) bytes of doubles, zeroed by the caller before a sweep:
+ *   acc[set * 9 + k], k < 8: the sum over batches of value k (the order of tdg_cgan_metrics' out) of set `set`; k = 8: the
+ *   batches added to that set;  acc[27]: the batches added to the moments;  acc[28 + p] / acc[28 + hw + p]: the sums over
+ *   batches of pixel p's batch mean / batch variance.
+ * counts: unsigned long long [3][4], per set the streaming threshold totals of tdg_cgan_metrics (hits 1..3, elements).
+ * tdg_cgan_eval_batch: ONE read of y f32 [n*hw] (10x depth) and pred gives the eight values of tdg_cgan_metrics for every set
+ *   in the bit mask `sets`:  1: prediction pred[i];  2: offset[i / hw] (nullable: 0);  4: image[i % hw] * image_scale (f32), a
+ *   per-pixel image broadcast over the batch.  Each set's values are ADDED to its sums in acc and its batch count advances;
+ *   out[5..7] enter as the RUNNING percentages after this batch.  Each set equals tdg_cgan_metrics on the same prediction
+ *   bit for bit before its f32 rounding (same block partition, same arithmetic).  Workspace: tdg_cgan_eval_workspace_bytes(). */
+int tdg_cgan_eval_batch(const float* y, const float* pred, const float* offset, const float* image, float image_scale, int n, int hw,
+                        int sets, unsigned long long* counts, double* acc, void* workspace, size_t workspace_bytes, void* stream);
+size_t tdg_cgan_eval_workspace_bytes(void);
+size_t tdg_cgan_eval_acc_bytes(int hw);
+/* tdg_cgan_eval_moments: tf.nn.moments(y, axes=0) of y f32 [n,hw] in float64, two passes: per pixel the batch mean and the mean
+ *   of the squared deviations from it, added to acc[28 + p] and acc[28 + hw + p]; acc[27] += 1. */
+int tdg_cgan_eval_moments(const float* y, int n, int hw, double* acc, void* stream);
+/* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
+ *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
+ *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */
+int tdg_cgan_eval_finish(const double* acc, const unsigned long long* counts, int hw, float unit, double* scalars, float* mean_img,
+                         float* var_img, void* stream);
 /* ---- paper_cgan full-frame inference (paper_fullimage.py; 3dgan_amd/csrc/tdg_cgan_full.hip) ----------------------------
  * The 65x65 window slides over an H x W frame at stride s (build_batch, :90-110): cols = (H - 93) / s windows down,
  * rows = (W - 93) / s across, P = cols * rows; patch c = n * cols + m (n < rows outer, m < cols inner) has its top-left

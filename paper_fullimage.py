@@ -65,20 +65,21 @@ def config_tokens(path):
     return out
 
 
-def parse_args(argv=None):
+def parse_args(argv=None, own=None, prog='paper_fullimage'):
     """train.py's arguments (3dgan_amd/arguments.parse_args) plus --strides / --split / --frames / --offset / --no_images.
-    `@file` arguments are expanded here, so that an options.config written by train.py parses."""
+    `@file` arguments are expanded here, so that an options.config written by train.py parses.  `own`: another driver's
+    parser of its own flags in place of own_parser() (paper_metrics.py), `prog` its name in the messages."""
     argv = sys.argv[1:] if argv is None else list(argv)
     expanded = []
     for a in argv:
         expanded += config_tokens(a[1:]) if a.startswith('@') else [a]
-    own, rest = own_parser().parse_known_args(expanded)
+    own, rest = (own or own_parser()).parse_known_args(expanded)
     args = importlib.import_module('3dgan_amd.arguments').parse_args(rest, warn=lambda m: sys.stderr.write(m + '\n'))
     for k, v in vars(own).items():
         setattr(args, k, v)
     if args.model != 'paper_cgan':
-        raise SystemExit('paper_fullimage: --model paper_cgan only (got %r)' % args.model)
-    if any(s < 1 for s in args.strides):
+        raise SystemExit('%s: --model paper_cgan only (got %r)' % (prog, args.model))
+    if any(s < 1 for s in getattr(args, 'strides', ())):
         raise SystemExit('paper_fullimage: every --strides value must be >= 1')
     return args
 
