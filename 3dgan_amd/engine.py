@@ -12,6 +12,7 @@ rounded up to 8 (zero padded); master weights, gradients and optimizer slots f32
 buckets; each conv keeps two packed copies of its filter (forward / backward-data GEMM
 operand layouts) that are refreshed after every optimizer step.
 """
+import collections
 import ctypes as C
 import math
 
@@ -23,17 +24,85 @@ from . import kernels as K
 from .ops import activations as A
 
 
-# ------------------------------------------------------------------------------ parameters
-class GraphRunner:
-    """Mixin: run a step body eagerly the first time (lazy workspaces, kernel attributes), capture it into a hipGraph
-    the second time and replay it afterwards.  Everything that varies per step must live at fixed device addresses
-    (batch staging buffer, Philox draw counter, Adam step count), so that a replay IS a new step.  Collectives and
+# ------------------------------------------------------------------------------ replicas
+Part = collections.namedtuple('Part', 'name store optimizer repack')
+
+
+def default_session(args):
+    from .runtime import Session
+    return Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
+
+
+class Replica:
+    """Base of every model replica: the surface checkpoint.py, train.py and bench.py rely on, stated once.
+
+    Parts: the trainable parts in checkpoint order, each a name, its ParamStore, its optimizer and the callable that
+    refreshes the packed GEMM operands from the store's masters (register()).
+
+    Graphs: a step body runs eagerly the first time (lazy workspaces, kernel attributes), is captured into a hipGraph
+    the second time and replayed afterwards (_run).  Everything that varies per step must live at fixed device addresses
+    (batch staging buffers, Philox draw counter, Adam step count), so that a replay IS a new step.  Collectives and
     host reads stay outside the captured bodies."""
 
-    def init_graphs(self, args, sess):
+    def __init__(self, args, sess=None):
+        self.args = args
+        self.sess = sess = sess or default_session(args)
+        self.parts, self._staging = [], ()
         # (--check_numerics keeps the graphs: the finite check runs between the captured bodies, never inside one)
         self.use_graphs = bool(getattr(args, 'use_graphs', True)) and sess.device.type == 'cuda'
         self._warm, self._graphs = set(), {}
+
+    @classmethod
+    def train_function(cls, x, args, sess=None):
+        """The gen-1 builder contract (train.py:246): `train_func(sess, args) -> loss dict`, the replica as `.replica`."""
+        replica = cls(x, args, sess)
+
+        def train_func(sess_=None, args_=None):
+            return replica.train_func(sess_, args_)
+        train_func.replica = replica
+        return train_func
+
+    # -- variables ---------------------------------------------------------------------------------
+    def register(self, name, store, optimizer, repack):
+        self.parts.append(Part(name, store, optimizer, repack))
+
+    def stores(self):
+        return [p.store for p in self.parts]
+
+    def optimizers(self):
+        return {'optimizers/' + p.name: p.optimizer for p in self.parts}
+
+    def refresh(self):
+        for p in self.parts:
+            p.repack()
+
+    def load_variables(self, arrays):
+        for store in self.stores():
+            store.load(arrays)
+        self.refresh()
+
+    def variables(self):
+        d = {}
+        for store in self.stores():
+            d.update(store.state_dict())
+        return d
+
+    def gradients(self):
+        d = {}
+        for store in self.stores():
+            d.update(store.grads_dict())
+        return d
+
+    # -- steps -------------------------------------------------------------------------------------
+    def staging(self, *shapes):
+        """f32 buffers the batch is copied into before every step: fixed addresses for the captured bodies."""
+        self._staging = tuple(torch.zeros(*s, dtype=torch.float32, device=self.sess.device) for s in shapes)
+        return self._staging
+
+    def _stage(self, batch):
+        """`batch`: one tensor per staging buffer, or the tensor itself when there is one buffer."""
+        for buf, t in zip(self._staging, batch if len(self._staging) > 1 else (batch,)):
+            buf.copy_(t.reshape(buf.shape))
 
     def _run(self, name, body):
         if not self.use_graphs or self.sess.inject:
@@ -52,7 +121,18 @@ class GraphRunner:
         self._graphs[name] = g
         g.replay()
 
+    def optimizer_step(self, store, grads, apply, what):
+        """One optimizer step on `store`; `grads` and `apply` are (graph name, body) pairs.  The finite check and the
+        exchange (util.average_gradients: RCCL all-reduce, the 1/n folded into the optimizer kernel) run between the two
+        captured bodies."""
+        self._run(*grads)
+        self.sess.assert_finite(store, what)
+        self._scale = self.sess.allreduce_mean_scale(store.grads)
+        self._run(*apply)
+        self.sess.global_step += 1
 
+
+# ------------------------------------------------------------------------------ parameters
 class ParamStore:
     """Flat f32 parameter / gradient buckets of one net with named views
     (names as in the reference: `generator/vars/fc1/weights`, `generator/BatchNorm/beta`)."""
@@ -108,6 +188,39 @@ def xavier_uniform_(t, shape, gen):
         fan_in, fan_out = rf * shape[-2], rf * shape[-1]
     lim = math.sqrt(6.0 / (fan_in + fan_out))
     t.copy_((torch.rand(shape, generator=gen, dtype=torch.float32) * 2 - 1) * lim)
+
+
+def init_variable(store, name, shape, init, gen):
+    """A fresh variable: xavier-uniform (weights and biases, App. A-4) or, for 'normal0.02' (pix2pix,
+    hem/models/pix2pix.py:180), N(0, 0.02)."""
+    cpu = torch.empty(shape, dtype=torch.float32)
+    if init == 'xavier':
+        xavier_uniform_(cpu, shape, gen)
+    else:
+        cpu.copy_(torch.randn(shape, generator=gen) * 0.02)
+    store[name].copy_(cpu)
+
+
+def declare_weights(store, net, layers):
+    """The `weights` / `bias` pair of each of `layers` of `net`, in that order."""
+    for l in layers:
+        store.declare(net.var_name(l, 'weights'), l.filter_shape)
+        store.declare(net.var_name(l, 'bias'), (l.out_size,))
+
+
+def init_weights(store, net, layers, gen):
+    """Fresh values for what declare_weights declared, drawn in the same order, each layer by its `spec.init`."""
+    for l in layers:
+        init_variable(store, net.var_name(l, 'weights'), l.filter_shape, l.init, gen)
+        init_variable(store, net.var_name(l, 'bias'), (l.out_size,), l.init, gen)
+
+
+def conv_pads(spec, big, small):
+    """(pad_t, pad_l) of the conv between `big` and `small`: TF's SAME split, none for VALID."""
+    if spec.padding != 'SAME':
+        return 0, 0
+    return (max((small.h - 1) * spec.stride + spec.k - big.h, 0) // 2,
+            max((small.w - 1) * spec.stride + spec.k - big.w, 0) // 2)
 
 
 # ------------------------------------------------------------------------------ optimizers
@@ -296,7 +409,7 @@ class SeqNet:
         prev = self.x
         for spec in net.layers:
             if getattr(spec, 'dropout', 0):
-                raise NotImplementedError('layer %s: dropout is only executed by the pix2pix U-Net (models/pix2pix.py)' % spec.name)
+                raise NotImplementedError('layer %s: dropout is only executed by the skip U-Net (unet.py)' % spec.name)
         prev_g = self.dx
         cum = 1
         for idx, spec in enumerate(net.layers):
@@ -348,12 +461,7 @@ class SeqNet:
                     big, small = L.h, L.inp
                 else:                                  # conv2d, dense, and conv A of a residual block
                     big, small = L.inp, L.h
-                if spec.padding == 'SAME':
-                    pt = max((small.h - 1) * spec.stride + spec.k - big.h, 0) // 2
-                    pl = max((small.w - 1) * spec.stride + spec.k - big.w, 0) // 2
-                else:
-                    pt = pl = 0
-                L.conv = K.Conv(big, small, spec.k, spec.k, spec.stride, pt, pl)
+                L.conv = K.Conv(big, small, spec.k, spec.k, spec.stride, *conv_pads(spec, big, small))
                 L.tan = K.Act(tangent_capacity * rpi, oh, ow, oc, dtype, device) if tangent_capacity else None
             self.layers.append(L)
             prev, prev_g = (L.h, L.gout) if not L.rowdot else (None, None)
@@ -367,8 +475,7 @@ class SeqNet:
             if L.spec.kind == 'residual':
                 L.res.declare(self.store)
                 continue
-            self.store.declare(L.wname, L.spec.filter_shape)
-            self.store.declare(L.bname, (L.spec.out_size,))
+            declare_weights(self.store, self.net, [L.spec])
             if L.spec.use_in:
                 for name in L.in_names:
                     self.store.declare(name, (L.spec.out_size,))
@@ -380,19 +487,15 @@ class SeqNet:
                     self.store.declare(L.bn_names[p], (L.spec.out_size,))
 
     def init_variables(self, gen):
-        """Fresh variables: xavier-uniform weights and biases, zero betas (App. A-3/A-4);
-        'normal0.02' (pix2pix, hem/models/pix2pix.py:180) draws N(0, 0.02)."""
+        """Fresh variables: weights and biases by `spec.init`, zero betas (App. A-3/A-4)."""
         for L in self.layers:
             if L.spec.use_in:
                 self.store[L.in_names[0]].fill_(1.0)        # scale: ones_initializer; shift stays at zeros (hem/ops/images.py:79-80)
-            pairs = L.res.variables() if L.spec.kind == 'residual' else ((L.wname, L.spec.filter_shape), (L.bname, (L.spec.out_size,)))
-            for name, shape in pairs:
-                cpu = torch.empty(shape, dtype=torch.float32)
-                if L.spec.init == 'xavier':
-                    xavier_uniform_(cpu, shape, gen)
-                else:
-                    cpu.copy_(torch.randn(shape, generator=gen) * 0.02)
-                self.store[name].copy_(cpu)
+            if L.spec.kind == 'residual':
+                for name, shape in L.res.variables():
+                    init_variable(self.store, name, shape, L.spec.init, gen)
+            else:
+                init_weights(self.store, self.net, [L.spec], gen)
 
     def repack(self):
         """Refresh the packed GEMM operands from the f32 masters (after every optimizer step)."""

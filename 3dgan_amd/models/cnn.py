@@ -17,7 +17,7 @@ from .. import kernels as K
 from .. import engine
 from ..ops.layers import dense, conv2d, deconv2d, flatten, reshape, arg_scope, variable_scope, placeholder, reset_graph
 from ..ops.activations import lrelu, relu, tanh
-from ..util import tower_scope_range, average_gradients, init_optimizer, collection_to_dict
+from ..util import tower_scope_range, init_optimizer, collection_to_dict
 
 
 def encoder(x, reuse=False):
@@ -54,9 +54,10 @@ def decoder(x, latent_size, out_channels=3, reuse=False):
     return x
 
 
-class CnnReplica(engine.GraphRunner):
+class CnnReplica(engine.Replica):
     def __init__(self, x_source, args, sess):
-        self.args, self.sess, self.x_source = args, sess, x_source
+        engine.Replica.__init__(self, args, sess)
+        self.x_source, sess = x_source, self.sess
         B, L = args.batch_size, args.latent_size
         h, w, c = args.image_shape
         if (h, w) != (64, 64):
@@ -82,59 +83,34 @@ class CnnReplica(engine.GraphRunner):
         self.E.declare_variables()
         (self.lat,) = lnet.layers
         self.wname, self.bname = lnet.var_name(self.lat, 'weights'), lnet.var_name(self.lat, 'bias')
-        self.store.declare(self.wname, self.lat.filter_shape)
-        self.store.declare(self.bname, (self.lat.out_size,))
+        engine.declare_weights(self.store, lnet, lnet.layers)
         self.Dn.declare_variables()
         self.store.allocate()
         gen = torch.Generator().manual_seed(sess.seed)
         self.E.init_variables(gen)
-        for name, shape in ((self.wname, self.lat.filter_shape), (self.bname, (self.lat.out_size,))):
-            cpu = torch.empty(shape)
-            engine.xavier_uniform_(cpu, shape, gen)
-            self.store[name].copy_(cpu)
+        engine.init_weights(self.store, lnet, lnet.layers, gen)
         self.Dn.init_variables(gen)
         self.opt = init_optimizer(args, self.store)
+        self.register('cnn', self.store, self.opt, self._repack)
 
         # latent dense: flat [B,512] -> z [B,L], written straight into the decoder's input
         e_last = self.E.layers[-1]
         self.flat = K.Act(B, 1, 1, 512, dt, dev, 512, e_last.h.buf)
         self.dflat = K.Act(B, 1, 1, 512, dt, dev, 512, e_last.gout.buf)
         self.lat_conv = K.Conv(self.flat, self.Dn.x, 1, 1, 1, 0, 0)
-        self.x_stage = torch.zeros(B, h, w, c, dtype=torch.float32, device=dev)
+        (self.x_stage,) = self.staging((B, h, w, c))
         self.scal = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.init_graphs(args, sess)
         self.refresh()
 
-    # ---- variables -----------------------------------------------------------------------------------
-    def stores(self):
-        return [self.store]
-
-    def optimizers(self):
-        return {'optimizers/cnn': self.opt}
-
-    def refresh(self):
+    def _repack(self):
         self.E.repack()
         self.Dn.repack()
         self.lat_conv.pack(self.store[self.wname].view(1, 1, 512, self.L), fwd=True, bwd=True)
 
-    def load_variables(self, arrays):
-        self.store.load(arrays)
-        self.refresh()
-
-    def variables(self):
-        return self.store.state_dict()
-
-    def gradients(self):
-        return self.store.grads_dict()
-
     # ---- one training step (util.py:22-28 default_training) -------------------------------------------------
     def step(self, x01):
-        self.x_stage.copy_(x01.reshape(self.x_stage.shape))      # fixed address: the bodies below may be graph-captured
-        self._run('grads', self._grads)
-        self.sess.assert_finite(self.store, 'cnn_step')
-        self._scale = average_gradients(self.sess, self.store)   # RCCL, outside the graphs
-        self._run('apply', self._apply)
-        self.sess.global_step += 1
+        self._stage(x01)
+        self.optimizer_step(self.store, ('grads', self._grads), ('apply', self._apply), 'cnn_step')
 
     def _apply(self):
         self.opt.step(self._scale)
@@ -179,11 +155,4 @@ class CnnReplica(engine.GraphRunner):
 
 def cnn(x, args, sess=None):
     """models/cnn.py:20-57."""
-    from ..runtime import Session
-    sess = sess or Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
-    replica = CnnReplica(x, args, sess)
-
-    def train_func(sess_=None, args_=None):
-        return replica.train_func(sess_, args_)
-    train_func.replica = replica
-    return train_func
+    return CnnReplica.train_function(x, args, sess)

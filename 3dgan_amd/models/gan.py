@@ -69,14 +69,15 @@ def discriminator(x, args, reuse=False):
 
 
 # ------------------------------------------------------------------------------ one replica
-class GanReplica(engine.GraphRunner):
+class GanReplica(engine.Replica):
     """The per-GPU replica ("tower") of models/gan.py:55-70 plus its optimizers (:46,79-81)."""
 
     # device scalar slots
     S_DREAL, S_DFAKE, S_SUMSQ, S_GP, S_GPCOEF, S_GLOSS_AUX, S_GAN_D, S_GAN_G = 0, 1, 2, 3, 4, 5, 6, 7
 
     def __init__(self, x_source, args, sess):
-        self.args, self.sess, self.x_source = args, sess, x_source
+        engine.Replica.__init__(self, args, sess)
+        self.x_source, sess = x_source, self.sess
         self.model = args.model
         B, L = args.batch_size, args.latent_size
         h, w, c = args.image_shape
@@ -129,42 +130,16 @@ class GanReplica(engine.GraphRunner):
         self.G.init_variables(gen)
         self.D.init_variables(gen)
         self.g_opt, self.d_opt = init_optimizer(args, self.g_store), init_optimizer(args, self.d_store)   # :46
+        self.register('generator', self.g_store, self.g_opt, self.G.repack)
+        self.register('discriminator', self.d_store, self.d_opt, self.D.repack)
         self.img_elems = self.D.x.image_elems        # channel-padded image size in HBM
-        # hipGraph replay of the two step bodies (launch-bound otherwise: ~600 small launches per iteration)
-        self.init_graphs(args, sess)
         # the conv layer with the largest filter: its gradient slice is exchanged first (d_step)
         self._d_big_layer = max(self.D.conv_layers(), key=lambda L: self.d_store[L.wname].numel())
-        self.x_stage = torch.zeros(B, h, w, c, dtype=torch.float32, device=dev)
+        (self.x_stage,) = self.staging((B, h, w, c))
         self._seed_g = None
         self.alpha = torch.zeros(B, dtype=torch.float32, device=dev)
         self.scal = torch.zeros(16, dtype=torch.float32, device=dev)
         self.refresh()
-
-    # -- variables ---------------------------------------------------------------------------------
-    def refresh(self):
-        self.G.repack()
-        self.D.repack()
-
-    def load_variables(self, arrays):
-        self.g_store.load(arrays)
-        self.d_store.load(arrays)
-        self.refresh()
-
-    def stores(self):
-        return [self.g_store, self.d_store]
-
-    def optimizers(self):
-        return {'optimizers/generator': self.g_opt, 'optimizers/discriminator': self.d_opt}
-
-    def variables(self):
-        d = self.g_store.state_dict()
-        d.update(self.d_store.state_dict())
-        return d
-
-    def gradients(self):
-        d = self.g_store.grads_dict()
-        d.update(self.d_store.grads_dict())
-        return d
 
     # -- pieces ------------------------------------------------------------------------------------
     def _load_real(self, x01):
@@ -173,8 +148,7 @@ class GanReplica(engine.GraphRunner):
         n = self.B * h * w * c
         if x01.dtype != torch.float32 or x01.numel() != n:
             raise ValueError('expected a float32 batch of %d values in [0,1], got %s %s' % (n, x01.dtype, tuple(x01.shape)))
-        self.x_stage.copy_(x01.reshape(self.x_stage.shape))          # fixed address: the step bodies may be graph-captured
-
+        self._stage(x01)
 
     def _rescale_real(self):
         h, w, c = self.args.image_shape
@@ -310,19 +284,16 @@ class GanReplica(engine.GraphRunner):
             self._scale = sess.allreduce_split(store.grads, lo, hi, between=lambda: self._run('d_grads_b', self._d_grads_b))
             sess.assert_finite(store, 'd_step')                       # after EVERY slice is summed: a NaN/Inf on one
                                                                       # replica is in every replica's bucket by now
+            self._run('d_apply', self._d_apply)
+            self.sess.global_step += 1
         elif sess.world_size == 1 and not sess.check_numerics and os.environ.get('TDG_ONE_BODY', '1') != '0':
             # one replica, nothing between the gradients and their update (no exchange, no finite check): ONE captured body --
             # every boundary between two graph launches is ~9 us of idle GPU, 6 of them per iteration here
             self._scale = 1.0
             self._run('d_step' + tag, self._d_grads_and_apply)
             self.sess.global_step += 1
-            return
         else:
-            self._run('d_grads' + tag, self._d_grads)
-            sess.assert_finite(store, 'd_step')
-            self._scale = average_gradients(sess, store)              # models/gan.py:77 (RCCL, outside the graphs)
-        self._run('d_apply', self._d_apply)
-        self.sess.global_step += 1
+            self.optimizer_step(store, ('d_grads' + tag, self._d_grads), ('d_apply', self._d_apply), 'd_step')   # models/gan.py:77
 
     def _d_grads_and_apply(self):
         self._d_grads()
@@ -400,17 +371,14 @@ class GanReplica(engine.GraphRunner):
             work.wait()
             sess.assert_finite(store, 'g_step')
             self._scale = 1.0 / sess.world_size
+            self._run('g_apply', self._g_apply)
+            self.sess.global_step += 1
         elif sess.world_size == 1 and not sess.check_numerics and os.environ.get('TDG_ONE_BODY', '1') != '0':
             self._scale = 1.0
             self._run('g_step', self._g_grads_and_apply)
             self.sess.global_step += 1
-            return
         else:
-            self._run('g_grads', self._g_grads)
-            sess.assert_finite(store, 'g_step')
-            self._scale = average_gradients(sess, store)              # models/gan.py:76
-        self._run('g_apply', self._g_apply)
-        self.sess.global_step += 1
+            self.optimizer_step(store, ('g_grads', self._g_grads), ('g_apply', self._g_apply), 'g_step')         # models/gan.py:76
 
     def _g_grads_critical(self):
         """g_loss = -mean(D(g)) and its gradient w.r.t. the generator: slot 1 only."""
@@ -524,11 +492,4 @@ class GanReplica(engine.GraphRunner):
 def gan(x, args, sess=None):
     """models/gan.py:39-91.  `x` is the per-replica input source (`.next_batch()` -> device float32
     [B, H, W, C] in [0,1]); returns the training function train.py:246,307 expects."""
-    from ..runtime import Session
-    sess = sess or Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
-    replica = GanReplica(x, args, sess)
-
-    def train_func(sess_=None, args_=None):
-        return replica.train_func(sess_, args_)
-    train_func.replica = replica
-    return train_func
+    return GanReplica.train_function(x, args, sess)

@@ -24,7 +24,7 @@ Dataset evaluation (paper/paper_metrics.py, the mean / variance image pre-pass o
 `metrics_y_mean`, :79,177): set_mean_image / dataset_moments / evaluate on the kernels of tdg_cgan_eval.hip; a sweep adds
 every batch into device-resident f64 accumulators and reads the host once.
 
-MI355X-native: activations are NHWC; the generator's skip concats are zero-copy channel windows (as models/pix2pix.py);
+MI355X-native: activations are NHWC; the generator runs on the skip U-Net executor (unet.py: zero-copy skip concats);
 D's rgb path runs ONCE over the B images -- it is identical for D(x, y) and D(x, y_hat) -- and its output fills the left
 window of both halves of the combined input (tdg_cgan_join), its backward sums the two halves' gradients first; the depth
 path and the 1x1 combined path run as one batched pass over 2B images; the 1x1 one-channel head computes the 29x29 crop
@@ -36,9 +36,9 @@ from ... import _lib
 from ... import kernels as K
 from ... import engine
 from ...ops.layers import conv2d, deconv2d, concat, arg_scope, variable_scope, placeholder, reset_graph
-from ...ops.activations import Activation
-from ..._lib import ACT_LRELU, ACT_RELU
-from ...util import tower_scope_range, average_gradients, collection_to_dict
+from ...ops.activations import _lrelu, relu
+from ...unet import UNet
+from ...util import tower_scope_range, collection_to_dict
 from ..ModelPlugin import ModelPlugin
 
 VERSIONS = {'baseline': 0, 'mean_adjusted': 1, 'mean_provided2': 2}
@@ -50,14 +50,7 @@ METRIC_KEYS = ('abs_rel_diff', 'squared_rel_diff', 'linear_rmse', 'log_rmse', 's
                'threshold1', 'threshold2', 'threshold3')
 
 
-def _lrelu(leak):
-    return Activation('lrelu', ACT_LRELU, leak)
-
-
-_relu = Activation('relu', ACT_RELU, 0.0)
-
-
-class paper_cgan(ModelPlugin, engine.GraphRunner):
+class paper_cgan(ModelPlugin, engine.Replica):
     name = 'paper_cgan'
 
     @staticmethod
@@ -92,7 +85,7 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         by the executor.  Returns (d4 output, the records of the decoder concats)."""
         B = args.batch_size
         with variable_scope('encoder'), arg_scope([conv2d], reuse=reuse, filter_size=5, stride=2, padding='VALID', init='xavier',
-                                                  activation=_relu):
+                                                  activation=relu):
             e1 = conv2d(x, x.shape[-1], 64, name='e1')          # 31x31x64
             e2 = conv2d(e1, 64, 128, name='e2')                 # 14x14x128
             e3 = conv2d(e2, 128, 256, name='e3')                # 5x5x256
@@ -151,9 +144,8 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
     S_GFAKE, S_DFAKE, S_DREAL, S_DTOTAL = 0, 1, 2, 3
 
     def __init__(self, x_y, args, sess=None):
-        from ...runtime import Session
-        self.args, self.x_y = args, x_y
-        self.sess = sess = sess or Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
+        engine.Replica.__init__(self, args, sess)
+        self.x_y, sess = x_y, self.sess
         for flag, default in paper_cgan._defaults().items():
             if not hasattr(args, flag):
                 setattr(args, flag, default)
@@ -181,8 +173,13 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         self.depth_g = self.Dd.layers[-1].gout
         # G input: D's rgb input where the two are the same tensor (baseline, mean_adjusted)
         self.gx = K.Act(B, SRC, SRC, 4, dt, dev) if mp2 else self.Dr.x
-        self.G = CganGenerator(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx,
-                               fake=self.Dd.x.view(B, B), dfake=self.Dd.dx.view(B, B))
+        # G: the U-Net hands over its last concat [d3 | e1]; the 1x1 head on the 29x29 crop is _generate / _g_backward
+        self.G = UNet(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx)
+        self.head = self.dec_net.layers[-1]
+        if len(self.dec_net.layers) != self.G.nd + 1 or (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.G.top.c):
+            raise ValueError('the generator head must be a 1x1 conv from the last concat to one channel')
+        self.head_ws = torch.zeros(B * (self.G.top.c + 1), dtype=torch.float32, device=dev)
+        self.fake, self.dfake = self.Dd.x.view(B, B), self.Dd.dx.view(B, B)      # g lands in D's fake depth input
         self.d_store.allocate()
         self.g_store.allocate()
         gen = torch.Generator().manual_seed(sess.seed)
@@ -195,8 +192,10 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         else:                                                # :67-69
             self.g_opt = engine.Adam(self.g_store, args.g_lr, args.g_beta1, args.g_beta2)
             self.d_opt = engine.Adam(self.d_store, args.d_lr, args.d_beta1, args.d_beta2)
+        self.register('generator', self.g_store, self.g_opt, self.G.repack)
+        self.register('discriminator', self.d_store, self.d_opt, self._repack_d)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        self.x_stage, self.y_stage = f32(B, SRC, SRC, 3), f32(B, SRC, SRC, 1)
+        self.x_stage, self.y_stage = self.staging((B, SRC, SRC, 3), (B, SRC, SRC, 1))
         self.ybar, self.crop, self.yhat = f32(B), f32(B, CROP, CROP), f32(B, CROP, CROP)     # of the last loss fetch
         self.inf_ybar, self.inf_crop, self.inf_yhat = f32(B), f32(B, CROP, CROP), f32(B, CROP, CROP)   # infer()'s own
         self.scal = f32(8)
@@ -216,50 +215,17 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         self.eval_scalars = f64(3, 12)
         self.eval_mean, self.eval_var = f32(CROP, CROP), f32(CROP, CROP)
         self.eval_ws = torch.zeros(lib.tdg_cgan_eval_workspace_bytes(), dtype=torch.uint8, device=dev)
-        self.init_graphs(args, sess)
         self.refresh()
 
     @staticmethod
     def _defaults():
         return {k.lstrip('-'): v['default'] for k, v in paper_cgan.arguments().items()}
 
-    # ---- variables -----------------------------------------------------------------------------------
-    def stores(self):
-        return [self.g_store, self.d_store]
-
-    def optimizers(self):
-        return {'optimizers/generator': self.g_opt, 'optimizers/discriminator': self.d_opt}
-
-    def refresh(self):
-        self.G.repack()
-        self._repack_d()
-
     def _repack_d(self):
         for net in (self.Dr, self.Dd, self.Dc):
             net.repack()
 
-    def load_variables(self, arrays):
-        self.g_store.load(arrays)
-        self.d_store.load(arrays)
-        self.refresh()
-
-    def variables(self):
-        d = self.g_store.state_dict()
-        d.update(self.d_store.state_dict())
-        return d
-
-    def gradients(self):
-        d = self.g_store.grads_dict()
-        d.update(self.d_store.grads_dict())
-        return d
-
     # ---- pieces ------------------------------------------------------------------------------------------
-    def _stage(self, batch):
-        """The batch at fixed device addresses (the step bodies are graph-captured)."""
-        x01, y01 = batch
-        self.x_stage.copy_(x01.reshape(self.x_stage.shape))
-        self.y_stage.copy_(y01.reshape(self.y_stage.shape))
-
     def _inputs(self, ybar, crop):
         """x into G's (and D's rgb) input, the depth target and the constant channels (:83-96, :286, :323, :326);
         y_bar and the f32 crop into `ybar` / `crop`."""
@@ -279,8 +245,23 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
                   self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs, K.stream())
 
     def _generate(self, ybar, yhat):
-        """g into D's fake depth input, y_hat = g (+ y_bar, :113-121) into `yhat`."""
-        self.G.forward(ybar if self.version != 0 else None, yhat)
+        """g (the cropped 1x1 head of the U-Net's last concat) into channel 0 of D's fake depth input, y_hat = g (+ y_bar,
+        :113-121) into `yhat` (f32)."""
+        self.G.forward()
+        c3, st, name = self.G.top, self.g_store, self.dec_net.var_name
+        _lib.call('tdg_cgan_head_fwd', self.sess.dtype, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP, K.ptr(st[name(self.head, 'weights')]),
+                  K.ptr(st[name(self.head, 'bias')]), K.ptr(ybar if self.version != 0 else None), K.ptr(yhat), self.fake.ptr(0),
+                  self.fake.cs, K.stream())
+
+    def _g_backward(self):
+        """From dL/dg in channel 0 of D's fake depth-input gradient: the head writes the last concat's gradient
+        [delta of d3 | dL/de1 from the skip] (the lrelu mask of d3 applied here, its producer), the U-Net takes it from there."""
+        c3, gc3, st, name = self.G.top, self.G.gtop, self.g_store, self.dec_net.var_name
+        _lib.call('tdg_cgan_head_bwd', self.sess.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP,
+                  K.ptr(st[name(self.head, 'weights')]), K.MASK_LRELU, self.dec_net.layers[-2].act.leak, gc3.ptr(),
+                  K.ptr(st.grad(name(self.head, 'weights'))), K.ptr(st.grad(name(self.head, 'bias'))),
+                  K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
+        self.G.backward()
 
     def _d_forward(self):
         B, dt = self.B, self.sess.dtype
@@ -309,11 +290,7 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
     # ---- steps ---------------------------------------------------------------------------------------------
     def d_step(self, batch):
         self._stage(batch)
-        self._run('d_grads', self._d_grads)
-        self.sess.assert_finite(self.d_store, 'd_step')
-        self._scale = average_gradients(self.sess, self.d_store)      # RCCL, outside the graphs
-        self._run('d_apply', self._d_apply)
-        self.sess.global_step += 1
+        self.optimizer_step(self.d_store, ('d_grads', self._d_grads), ('d_apply', self._d_apply), 'd_step')
 
     def _d_grads(self):
         B, dt = self.B, self.sess.dtype
@@ -335,11 +312,7 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
 
     def g_step(self, batch):
         self._stage(batch)
-        self._run('g_grads', self._g_grads)
-        self.sess.assert_finite(self.g_store, 'g_step')
-        self._scale = average_gradients(self.sess, self.g_store)
-        self._run('g_apply', self._g_apply)
-        self.sess.global_step += 1
+        self.optimizer_step(self.g_store, ('g_grads', self._g_grads), ('g_apply', self._g_apply), 'g_step')
 
     def _g_grads(self):
         """The G step and the loss fetch of one sess.run (:208): D runs on both halves, the losses are this batch's."""
@@ -353,7 +326,7 @@ class paper_cgan(ModelPlugin, engine.GraphRunner):
         dx = self.Dc.dx
         _lib.call('tdg_cgan_join', dt, 1, B, B, 512, dx.ptr(B), dx.cs, None, 0, self.depth_g.ptr(B), self.depth_g.cs, K.stream())
         self.Dd.backward(B, B, want_params=False, want_dx=True)
-        self.G.backward()
+        self._g_backward()
 
     def _g_apply(self):
         self.g_opt.step(self._scale)
@@ -596,117 +569,3 @@ def patch_grid(H, W, stride):
         raise ValueError('patch_grid: stride %d < 1' % stride)
     span = SRC + CROP - 1
     return PatchGrid((H - span) // stride, (W - span) // stride, stride)
-
-
-# ------------------------------------------------------------------------------------------------------
-class CganGenerator:
-    """The 4-down / 3-up generator with zero-copy skip concats and the cropped 1x1 head.
-
-    cat[1] = [d1 | e3] (5x5x512), cat[2] = [d2 | e2] (14x14x256), cat[3] = [d3 | e1] (31x31x128); gcat[i] their gradients.
-    Encoder layer k (k <= 3) writes its activation into the right window of cat[4-k] and receives its gradient -- skip path
-    first, main path accumulated on top -- in the right window of gcat[4-k], as models/pix2pix.py's UNet.
-    """
-
-    def __init__(self, enet, dnet, B, dtype, device, store, ws, x_in, fake, dfake):
-        self.B, self.dtype, self.store, self.ws = B, dtype, store, ws
-        self.enet, self.dnet = enet, dnet
-        E, Dc = enet.layers, dnet.layers
-        assert len(E) == 4 and len(Dc) == 4
-        A = lambda h, w, c: K.Act(B, h, w, c, dtype, device)
-        self.x_in, self.fake, self.dfake = x_in, fake, dfake
-        sizes = [E[k].out_shape for k in range(4)]                 # (31,31,64) (14,14,128) (5,5,256) (1,1,512)
-        self.cat, self.gcat = {}, {}
-        for i in range(1, 4):
-            cd, ce = Dc[i - 1].out_size, E[3 - i].out_size
-            h, w, _ = sizes[3 - i]
-            if Dc[i].in_size != cd + ce:
-                raise ValueError('decoder layer %d expects %d input channels, skip concat provides %d' % (i + 1, Dc[i].in_size, cd + ce))
-            self.cat[i], self.gcat[i] = A(h, w, cd + ce), A(h, w, cd + ce)
-        self.e_h, self.e_g = {}, {}
-        for k in range(1, 5):
-            co = E[k - 1].out_size
-            if k <= 3:
-                cd = Dc[3 - k].out_size
-                self.e_h[k], self.e_g[k] = self.cat[4 - k].window(cd, co), self.gcat[4 - k].window(cd, co)
-            else:
-                self.e_h[k], self.e_g[k] = A(1, 1, co), A(1, 1, co)
-        self.d_h = {i: self.cat[i].window(0, Dc[i - 1].out_size) for i in range(1, 4)}
-        self.d_g = {i: self.gcat[i].window(0, Dc[i - 1].out_size) for i in range(1, 4)}
-        self.head = Dc[3]
-        if (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.cat[3].c):
-            raise ValueError('the generator head must be a 1x1 conv from the last concat to one channel')
-        self.e_conv = {k: K.Conv(self.x_in if k == 1 else self.e_h[k - 1], self.e_h[k], 5, 5, 2, 0, 0) for k in range(1, 5)}
-        self.d_conv = {i: K.Conv(self.d_h[i], self.e_h[4] if i == 1 else self.cat[i - 1], 5, 5, 2, 0, 0) for i in range(1, 4)}
-        for net in (enet, dnet):
-            for l in net.layers:
-                store.declare(net.var_name(l, 'weights'), l.filter_shape)
-                store.declare(net.var_name(l, 'bias'), (l.out_size,))
-        self._pack_jobs = None
-        self.head_ws = torch.zeros(B * (self.cat[3].c + 1), dtype=torch.float32, device=device)
-
-    def init_variables(self, gen):
-        for net in (self.enet, self.dnet):
-            for l in net.layers:
-                for which, shape in (('weights', l.filter_shape), ('bias', (l.out_size,))):
-                    cpu = torch.empty(shape, dtype=torch.float32)
-                    engine.xavier_uniform_(cpu, shape, gen)
-                    self.store[net.var_name(l, which)].copy_(cpu)
-
-    def repack(self):
-        if self._pack_jobs is None:
-            jl = [self.e_conv[k].pack_job(self.store[self.enet.var_name(self.enet.layers[k - 1], 'weights')]) for k in range(1, 5)]
-            jl += [self.d_conv[i].pack_job(self.store[self.dnet.var_name(self.dnet.layers[i - 1], 'weights')]) for i in range(1, 4)]
-            self._pack_jobs = K.make_pack_jobs(jl)
-        K.pack_all(self._pack_jobs)
-
-    def _var(self, net, l, which):
-        return self.store[net.var_name(l, which)]
-
-    def forward(self, ybar, yhat):
-        """g into channel 0 of D's fake depth input, y_hat = g (+ y_bar when given) into `yhat` (f32)."""
-        B = self.B
-        E, Dc = self.enet.layers, self.dnet.layers
-        for k in range(1, 5):
-            spec = E[k - 1]
-            src = self.x_in if k == 1 else self.e_h[k - 1]
-            self.e_conv[k].fwd(src.ptr(), self.e_h[k].ptr(), B,
-                               K.epilogue(bias=self._var(self.enet, spec, 'bias'), act=spec.act.code, leak=spec.act.leak))
-        for i in range(1, 4):
-            spec = Dc[i - 1]
-            src = self.e_h[4] if i == 1 else self.cat[i - 1]
-            self.d_conv[i].bwd_data(src.ptr(), self.d_h[i].ptr(), B,
-                                    K.epilogue(bias=self._var(self.dnet, spec, 'bias'), act=spec.act.code, leak=spec.act.leak))
-        c3 = self.cat[3]
-        _lib.call('tdg_cgan_head_fwd', self.dtype, c3.ptr(), B, c3.h, c3.c, c3.cs, CROP, K.ptr(self._var(self.dnet, self.head, 'weights')),
-                  K.ptr(self._var(self.dnet, self.head, 'bias')), K.ptr(ybar), K.ptr(yhat), self.fake.ptr(0), self.fake.cs, K.stream())
-
-    def backward(self):
-        """From dL/dg in channel 0 of D's fake depth-input gradient."""
-        B, st, g = self.B, self.store, self.store.grad
-        E, Dc = self.enet.layers, self.dnet.layers
-        c3, gc3 = self.cat[3], self.gcat[3]
-        _lib.call('tdg_cgan_head_bwd', self.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), B, c3.h, c3.c, c3.cs, CROP,
-                  K.ptr(st[self.dnet.var_name(self.head, 'weights')]), K.MASK_LRELU, Dc[2].act.leak, gc3.ptr(),
-                  K.ptr(g(self.dnet.var_name(self.head, 'weights'))), K.ptr(g(self.dnet.var_name(self.head, 'bias'))),
-                  K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
-        # gcat[i] now holds [delta of d_i | dL/de_{4-i} from the skip] (the lrelu mask of d_i applied by its producer)
-        for i in range(3, 0, -1):
-            spec, conv = Dc[i - 1], self.d_conv[i]
-            delta = self.d_g[i]
-            K.bias_grad(self.ws, delta, spec.out_size, g(self.dnet.var_name(spec, 'bias')))
-            src = self.e_h[4] if i == 1 else self.cat[i - 1]
-            conv.bwd_filter(delta.ptr(), src.ptr(), g(self.dnet.var_name(spec, 'weights')), B, 0.0)
-            if i > 1:      # first writer of gcat[i-1], both windows; lrelu'(cat) is exact on d's window, 1 on e's where e > 0
-                conv.fwd(delta.ptr(), self.gcat[i - 1].ptr(), B,
-                         K.epilogue(mask_mode=K.MASK_LRELU, leak=Dc[i - 2].act.leak, mask_src=self.cat[i - 1].ptr()))
-            else:
-                conv.fwd(delta.ptr(), self.e_g[4].ptr(), B, K.epilogue(mask_mode=K.MASK_RELU, mask_src=self.e_h[4].ptr()))
-        for k in range(4, 0, -1):
-            spec, conv = E[k - 1], self.e_conv[k]
-            delta = self.e_g[k]
-            K.bias_grad(self.ws, delta, spec.out_size, g(self.enet.var_name(spec, 'bias')))
-            src = self.x_in if k == 1 else self.e_h[k - 1]
-            conv.bwd_filter(src.ptr(), delta.ptr(), g(self.enet.var_name(spec, 'weights')), B, 0.0)
-            if k > 1:      # + the main path on top of the skip gradient, then relu'(e_{k-1})
-                conv.bwd_data(delta.ptr(), self.e_g[k - 1].ptr(), B,
-                              K.epilogue(mask_mode=K.MASK_RELU, mask_src=self.e_h[k - 1].ptr(), accumulate=True))

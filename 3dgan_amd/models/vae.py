@@ -23,7 +23,7 @@ from .. import kernels as K
 from .. import engine
 from ..ops.layers import dense, conv2d, deconv2d, flatten, reshape, random_normal, arg_scope, variable_scope, placeholder, reset_graph
 from ..ops.activations import lrelu, relu, sigmoid
-from ..util import tower_scope_range, average_gradients, init_optimizer, collection_to_dict
+from ..util import tower_scope_range, init_optimizer, collection_to_dict
 
 
 def encoder(x, reuse=False):
@@ -63,11 +63,12 @@ def decoder(x, latent_size, out_channels=3, reuse=False):
     return x
 
 
-class VaeReplica(engine.GraphRunner):
+class VaeReplica(engine.Replica):
     S_DLOSS, S_LLOSS = 0, 1
 
     def __init__(self, x_source, args, sess):
-        self.args, self.sess, self.x_source = args, sess, x_source
+        engine.Replica.__init__(self, args, sess)
+        self.x_source, sess = x_source, self.sess
         B, L = args.batch_size, args.latent_size
         h, w, c = args.image_shape
         if (h, w) != (64, 64):
@@ -91,20 +92,15 @@ class VaeReplica(engine.GraphRunner):
         self.E = engine.SeqNet(enet, B, (h, w, c), dt, dev, self.store, ws=self.ws)
         self.Dn = engine.SeqNet(dnet, B, (1, 1, L), dt, dev, self.store, need_input_grad=True, ws=self.ws)
         self.E.declare_variables()
-        for l in lnet.layers:                                       # latent/vars/d1, d2 under their own names
-            self.store.declare(lnet.var_name(l, 'weights'), l.filter_shape)
-            self.store.declare(lnet.var_name(l, 'bias'), (l.out_size,))
+        engine.declare_weights(self.store, lnet, lnet.layers)      # latent/vars/d1, d2 under their own names
         self.Dn.declare_variables()
         self.store.allocate()
         gen = torch.Generator().manual_seed(sess.seed)
         self.E.init_variables(gen)
-        for l in lnet.layers:
-            for which, shape in (('weights', l.filter_shape), ('bias', (l.out_size,))):
-                cpu = torch.empty(shape)
-                engine.xavier_uniform_(cpu, shape, gen)
-                self.store[lnet.var_name(l, which)].copy_(cpu)
+        engine.init_weights(self.store, lnet, lnet.layers, gen)
         self.Dn.init_variables(gen)
         self.opt = init_optimizer(args, self.store)
+        self.register('vae', self.store, self.opt, self._repack)
 
         # fused latent heads: flat [B,512] -> [B, 2L] = [mean | std]
         e_last = self.E.layers[-1]
@@ -118,19 +114,11 @@ class VaeReplica(engine.GraphRunner):
         self.dw_heads = torch.zeros_like(self.w_heads)
         self.db_heads = torch.zeros_like(self.b_heads)
         self.eps = K.Act(B, 1, 1, L, dt, dev)
-        self.x_stage = torch.zeros(B, h, w, c, dtype=torch.float32, device=dev)
+        (self.x_stage,) = self.staging((B, h, w, c))
         self.scal = torch.zeros(8, dtype=torch.float32, device=dev)
-        self.init_graphs(args, sess)
         self.refresh()
 
-    # ---- variables -----------------------------------------------------------------------------------
-    def stores(self):
-        return [self.store]
-
-    def optimizers(self):
-        return {'optimizers/vae': self.opt}
-
-    def refresh(self):
+    def _repack(self):
         L = self.L
         self.E.repack()
         self.Dn.repack()
@@ -140,24 +128,10 @@ class VaeReplica(engine.GraphRunner):
         self.b_heads[L:].copy_(self.store['latent/vars/d2/bias'])
         self.head_conv.pack(self.w_heads, fwd=True, bwd=True)
 
-    def load_variables(self, arrays):
-        self.store.load(arrays)
-        self.refresh()
-
-    def variables(self):
-        return self.store.state_dict()
-
-    def gradients(self):
-        return self.store.grads_dict()
-
     # ---- one training step (util.py:22-28 default_training) -------------------------------------------------
     def step(self, x01):
-        self.x_stage.copy_(x01.reshape(self.x_stage.shape))      # fixed address: the bodies below may be graph-captured
-        self._run('grads', self._grads)
-        self.sess.assert_finite(self.store, 'vae_step')
-        self._scale = average_gradients(self.sess, self.store)   # RCCL, outside the graphs
-        self._run('apply', self._apply)
-        self.sess.global_step += 1
+        self._stage(x01)
+        self.optimizer_step(self.store, ('grads', self._grads), ('apply', self._apply), 'vae_step')
 
     def _apply(self):
         self.opt.step(self._scale)
@@ -210,11 +184,4 @@ class VaeReplica(engine.GraphRunner):
 
 def vae(x, args, sess=None):
     """models/vae.py:25-51."""
-    from ..runtime import Session
-    sess = sess or Session(dtype=getattr(args, 'dtype_code', K.BF16), seed=getattr(args, 'seed', 0) or 0)
-    replica = VaeReplica(x, args, sess)
-
-    def train_func(sess_=None, args_=None):
-        return replica.train_func(sess_, args_)
-    train_func.replica = replica
-    return train_func
+    return VaeReplica.train_function(x, args, sess)

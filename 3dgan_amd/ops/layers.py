@@ -241,7 +241,7 @@ def _norm_flags(name, use_batch_norm, use_batch_renorm, use_instance_norm):
 
 def concat(xs, axis=-1):
     """tf.concat along channels (axis=1 in the reference's NCHW == last axis in NHWC).  Executed as a
-    zero-copy concat: producers write their channel window of one buffer (models/pix2pix.py)."""
+    zero-copy concat: producers write their channel window of one buffer (unet.py)."""
     base = xs[0].shape[:-1]
     for t in xs:
         if t.shape[:-1] != base:
