@@ -3127,7 +3127,7 @@ struct ThinFwdArgs {
   int TH, tiles_per_image, ntiles_n;
   int PH, PW;             // staged patch (pixels), 4 elements per pixel
   int y_off, k_off;       // LDS byte offsets of the patch and of the k table
-  int act, mask_mode;
+  int act, mask_mode, accumulate;
   float leak;
   int debug;              // TDG_DEBUG_ABLATE (diagnostics): 7 = no global stores, 8 = no MFMA loop
   unsigned long long* stamps;   // diagnostic build (-DTDG_STAMPS) only: per-wave phase boundaries; null otherwise
@@ -3276,6 +3276,11 @@ __global__ void __launch_bounds__(256, 2) thin_fwd_kernel(const ThinFwdArgs a) {
     if (n >= a.N || a.debug == 7) continue;
     bf16x8 v = *reinterpret_cast<const bf16x8*>(sE + row * PE + cc * 16);
     const size_t o = (size_t)row * a.Cso + n;
+    if (a.accumulate) {                                     // (the staged bf16 value + out: the filter exists in this kernel's layout only)
+      const bf16x8 ov = *reinterpret_cast<const bf16x8*>(yi + o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (bf16_t)((float)v[e] + (float)ov[e]);
+    }
     if (a.mask_mode != TDG_MASK_NONE) {
       const bf16x8 mv = *reinterpret_cast<const bf16x8*>(a.mask_src + ((size_t)img * a.OH + oy0) * a.OW * a.Cso + o);
 #pragma unroll
@@ -4390,7 +4395,7 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
   TDG_CHECK_ARG(!p.veca || ((uintptr_t)x & 15) == 0, "tdg_conv2d_fwd: x must be 16-byte aligned (channel stride allows the vector gather)");
   const hipStream_t s = (hipStream_t)stream;
   const double flops = conv_flops(d, n_images);
-  if (p.thin && !(epi && epi->accumulate)) {
+  if (p.thin) {                                              // (the filter is packed in thin_fwd_kernel's layout: no other kernel can read it)
     const ThinPlan& tp = p.tp;
     ThinFwdArgs f;
     memset(&f, 0, sizeof(f));

@@ -78,7 +78,8 @@ typedef struct TdgEpilogue {
    * sum (v - bias[n])^2 of the stored pre-activation = the batch statistics of tf.contrib.layers.batch_norm
    * (ops/layers.py:103,144).  Only rows of images < col_images count (0: all).  The launch reports how many row
    * tiles it wrote in *col_nblk_out (host memory, written before the call returns); 0 = this launch's kernel
-   * variant does not provide partials (f32 tiles, accumulating epilogues, thin layers): run the separate pass.
+   * variant does not provide partials (f32 tiles, accumulating epilogues, thin layers -- the thin-input, one-output-channel
+   * and register-staged kernels --, and launches cut along K, whose tiles are not the stored tile): run the separate pass.
    * Finish with tdg_col_finalize_sum / tdg_bn_fwd_from_partials. */
   float* col_partial;
   size_t col_partial_bytes;
