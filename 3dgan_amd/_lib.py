@@ -94,6 +94,8 @@ SIGNATURES = {
     'tdg_cgan_prep': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     'tdg_cgan_head_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     'tdg_cgan_head_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_head_noise_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'tdg_cgan_head_noise_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_join': (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     'tdg_cgan_wgan_loss': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'tdg_cgan_metrics': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -103,6 +105,8 @@ SIGNATURES = {
     'tdg_cgan_eval_acc_bytes': (_sz, [_i]),
     'tdg_cgan_eval_moments': (_i, [_vp, _i, _i, _vp, _vp]),
     'tdg_cgan_eval_finish': (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
+    'tdg_cgan_sample_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_sample_stats_workspace_bytes': (_sz, [_i, _i]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -104,10 +104,13 @@ __global__ void __launch_bounds__(256) cgan_prep_kernel(const float* __restrict_
 
 // ---- generator head: G = w . cat + b on the top-left crop x crop pixels of the hw x hw concat -------------------
 // TPP threads per pixel, eight channels each (cin = 8 * TPP); the dot product is finished by a butterfly in the group.
-template <typename T, int TPP>
+// NOISE (paper_sampler --noise_layer d4): the head is a cin + 1 -> 1 conv whose last input channel is the f32 draw
+// u [n,hw,hw], read in place of a widened concat: g = w . cat + w[cin] * u + b.  g32 (nullable): g as f32 [n,crop,crop].
+template <typename T, int TPP, bool NOISE>
 __global__ void __launch_bounds__(256) cgan_head_fwd_kernel(const T* __restrict__ cat, int hw, int cs, int crop,
                                                             const float* __restrict__ w, const float* __restrict__ bias,
-                                                            const float* __restrict__ ybar, float* __restrict__ yhat,
+                                                            const float* __restrict__ u, const float* __restrict__ ybar,
+                                                            float* __restrict__ yhat, float* __restrict__ g32,
                                                             T* __restrict__ fake, int fcs) {
   const int b = blockIdx.x, lane = threadIdx.x % TPP, grp = threadIdx.x / TPP;
   constexpr int G = 256 / TPP;
@@ -115,6 +118,7 @@ __global__ void __launch_bounds__(256) cgan_head_fwd_kernel(const T* __restrict_
 #pragma unroll
   for (int i = 0; i < 8; ++i) wv[i] = w[lane * 8 + i];
   const float b0 = bias[0], off = ybar ? ybar[b] : 0.f;
+  const float wn = NOISE ? w[8 * TPP] : 0.f;
   const int npix = crop * crop;
   for (int p = grp; p < npix; p += G) {
     const int r = p / crop, c = p - r * crop;
@@ -126,27 +130,32 @@ __global__ void __launch_bounds__(256) cgan_head_fwd_kernel(const T* __restrict_
 #pragma unroll
     for (int o = TPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (lane == 0) {
+      if constexpr (NOISE) s = fmaf(wn, u[(size_t)b * hw * hw + (size_t)r * hw + c], s);
       const float g = s + b0;
       yhat[(size_t)b * npix + p] = g + off;
+      if (g32) g32[(size_t)b * npix + p] = g;
       fake[((size_t)b * npix + p) * fcs] = from_f32<T>(g);
     }
   }
 }
 
 // ---- generator head backward: dcat = delta (x) w * mask(cat) on every pixel (zero outside the crop); per-image
-// partials of dW = sum delta * cat and db = sum delta, finished in a fixed order by cgan_head_finish_kernel
-template <typename T, int TPP>
+// partials of dW = sum delta * cat and db = sum delta, finished in a fixed order by cgan_head_finish_kernel.
+// NOISE: one more partial column, dW[cin] = sum delta * u, between dW[0:cin] and db; the draw gets no gradient.
+template <typename T, int TPP, bool NOISE>
 __global__ void __launch_bounds__(256) cgan_head_bwd_kernel(const T* __restrict__ dfake, int fcs, const T* __restrict__ cat, int hw,
-                                                            int cs, int crop, const float* __restrict__ w, int mmode, float leak,
+                                                            int cs, int crop, const float* __restrict__ w,
+                                                            const float* __restrict__ u, int mmode, float leak,
                                                             T* __restrict__ dcat, float* __restrict__ partial) {
-  constexpr int G = 256 / TPP, CIN = 8 * TPP;
+  constexpr int G = 256 / TPP, CIN = 8 * TPP, COLS = CIN + (NOISE ? 2 : 1);
   __shared__ float acc_sh[G][CIN];
   __shared__ float db_sh[G];
+  __shared__ float dn_sh[G];
   const int b = blockIdx.x, lane = threadIdx.x % TPP, grp = threadIdx.x / TPP;
   float wv[8], acc[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { wv[i] = w[lane * 8 + i]; acc[i] = 0.f; }
-  float dbacc = 0.f;
+  float dbacc = 0.f, dnacc = 0.f;
   for (int p = grp; p < hw * hw; p += G) {
     const int r = p / hw, c = p - r * hw;
     const size_t o = ((size_t)b * hw * hw + p) * cs + lane * 8;
@@ -161,6 +170,7 @@ __global__ void __launch_bounds__(256) cgan_head_bwd_kernel(const T* __restrict_
         out[i] = d * wv[i] * mask_factor(v[i], mmode, leak);
       }
       dbacc += d;
+      if constexpr (NOISE) dnacc = fmaf(d, u[(size_t)b * hw * hw + p], dnacc);
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) out[i] = 0.f;
@@ -169,12 +179,12 @@ __global__ void __launch_bounds__(256) cgan_head_bwd_kernel(const T* __restrict_
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc_sh[grp][lane * 8 + i] = acc[i];
-  if (lane == 0) db_sh[grp] = dbacc;
+  if (lane == 0) { db_sh[grp] = dbacc; dn_sh[grp] = dnacc; }
   __syncthreads();
-  float* pi = partial + (size_t)b * (CIN + 1);
-  for (int ch = threadIdx.x; ch <= CIN; ch += 256) {
+  float* pi = partial + (size_t)b * COLS;
+  for (int ch = threadIdx.x; ch < COLS; ch += 256) {
     float s = 0.f;
-    for (int g = 0; g < G; ++g) s += ch < CIN ? acc_sh[g][ch] : db_sh[g];
+    for (int g = 0; g < G; ++g) s += ch < CIN ? acc_sh[g][ch] : (ch == COLS - 1 ? db_sh[g] : dn_sh[g]);
     pi[ch] = s;
   }
 }
@@ -303,20 +313,67 @@ extern "C" int tdg_cgan_prep(int dtype, const float* y, int n, int version, void
     default: tdg_set_error("tdg_cgan_head: cin %d is not 64, 128, 256 or 512", (cin)); return TDG_EINVAL; \
   }
 
+// both head forwards: u == nullptr is the cin -> 1 head, else the cin + 1 -> 1 head of --noise_layer d4
+static int head_fwd(const char* what, int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w,
+                    const float* b, const float* u, const float* ybar, float* yhat, float* g32, void* fake, int fake_cs,
+                    hipStream_t stream) {
+  tdg_timing_start(what, 0.0, stream);
+  DISPATCH_T(dtype, {
+    CGAN_TPP_DISPATCH(cin, {
+      if (u)
+        hipLaunchKernelGGL((cgan_head_fwd_kernel<T, TPP, true>), dim3(n), dim3(256), 0, stream, static_cast<const T*>(cat), hw, cs,
+                           crop, w, b, u, ybar, yhat, g32, static_cast<T*>(fake), fake_cs);
+      else
+        hipLaunchKernelGGL((cgan_head_fwd_kernel<T, TPP, false>), dim3(n), dim3(256), 0, stream, static_cast<const T*>(cat), hw, cs,
+                           crop, w, b, u, ybar, yhat, g32, static_cast<T*>(fake), fake_cs);
+    })
+  })
+  tdg_timing_stop(stream);
+  TDG_HIP_LAUNCH_CHECK(what);
+  return TDG_OK;
+}
+
+static int head_bwd(const char* what, int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs,
+                    int crop, const float* w, const float* u, int mask_mode, float leak, void* dcat, float* dw, float* db,
+                    void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const int cols = cin + (u ? 2 : 1);
+  if (workspace_bytes < (size_t)n * cols * sizeof(float)) {
+    tdg_set_error("%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, (size_t)n * cols * sizeof(float));
+    return TDG_EWORKSPACE;
+  }
+  float* part = static_cast<float*>(workspace);
+  tdg_timing_start(what, 0.0, stream);
+  DISPATCH_T(dtype, {
+    CGAN_TPP_DISPATCH(cin, {
+      if (u)
+        hipLaunchKernelGGL((cgan_head_bwd_kernel<T, TPP, true>), dim3(n), dim3(256), 0, stream, static_cast<const T*>(dfake), fake_cs,
+                           static_cast<const T*>(cat), hw, cs, crop, w, u, mask_mode, leak, static_cast<T*>(dcat), part);
+      else
+        hipLaunchKernelGGL((cgan_head_bwd_kernel<T, TPP, false>), dim3(n), dim3(256), 0, stream, static_cast<const T*>(dfake), fake_cs,
+                           static_cast<const T*>(cat), hw, cs, crop, w, u, mask_mode, leak, static_cast<T*>(dcat), part);
+    })
+  })
+  hipLaunchKernelGGL(cgan_head_finish_kernel, dim3(tdg_ceil_div(cols, 256)), dim3(256), 0, stream, part, n, cols, dw, db);
+  tdg_timing_stop(stream);
+  TDG_HIP_LAUNCH_CHECK(what);
+  return TDG_OK;
+}
+
 extern "C" int tdg_cgan_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w,
                                  const float* b, const float* ybar, float* yhat, void* fake, int fake_cs, void* stream) {
   TDG_CHECK_ARG(cat && w && b && yhat && fake && n > 0 && crop > 0 && crop <= hw && cs >= cin && cs % 8 == 0 && fake_cs > 0,
                 "tdg_cgan_head_fwd: bad argument");
-  tdg_timing_start("cgan_head_fwd", 0.0, (hipStream_t)stream);
-  DISPATCH_T(dtype, {
-    CGAN_TPP_DISPATCH(cin, {
-      hipLaunchKernelGGL((cgan_head_fwd_kernel<T, TPP>), dim3(n), dim3(256), 0, (hipStream_t)stream, static_cast<const T*>(cat), hw,
-                         cs, crop, w, b, ybar, yhat, static_cast<T*>(fake), fake_cs);
-    })
-  })
-  tdg_timing_stop((hipStream_t)stream);
-  TDG_HIP_LAUNCH_CHECK("cgan_head_fwd");
-  return TDG_OK;
+  return head_fwd("cgan_head_fwd", dtype, cat, n, hw, cin, cs, crop, w, b, nullptr, ybar, yhat, nullptr, fake, fake_cs,
+                  (hipStream_t)stream);
+}
+
+extern "C" int tdg_cgan_head_noise_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w,
+                                       const float* b, const float* u, const float* ybar, float* yhat, float* g, void* fake,
+                                       int fake_cs, void* stream) {
+  TDG_CHECK_ARG(cat && w && b && yhat && fake && n > 0 && crop > 0 && crop <= hw && cs >= cin && cs % 8 == 0 && fake_cs > 0,
+                "tdg_cgan_head_noise_fwd: bad argument");
+  return head_fwd("cgan_head_noise_fwd", dtype, cat, n, hw, cin, cs, crop, w, b, u, ybar, yhat, g, fake, fake_cs,
+                  (hipStream_t)stream);
 }
 
 extern "C" int tdg_cgan_head_bwd(int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs, int crop,
@@ -325,23 +382,18 @@ extern "C" int tdg_cgan_head_bwd(int dtype, const void* dfake, int fake_cs, cons
   TDG_CHECK_ARG(dfake && cat && w && dcat && dw && db && workspace && n > 0 && crop > 0 && crop <= hw && cs >= cin && cs % 8 == 0 &&
                     fake_cs > 0,
                 "tdg_cgan_head_bwd: bad argument");
-  if (workspace_bytes < (size_t)n * (cin + 1) * sizeof(float)) {
-    tdg_set_error("tdg_cgan_head_bwd: workspace of %zu bytes, %zu needed", workspace_bytes, (size_t)n * (cin + 1) * sizeof(float));
-    return TDG_EWORKSPACE;
-  }
-  float* part = static_cast<float*>(workspace);
-  tdg_timing_start("cgan_head_bwd", 0.0, (hipStream_t)stream);
-  DISPATCH_T(dtype, {
-    CGAN_TPP_DISPATCH(cin, {
-      hipLaunchKernelGGL((cgan_head_bwd_kernel<T, TPP>), dim3(n), dim3(256), 0, (hipStream_t)stream, static_cast<const T*>(dfake),
-                         fake_cs, static_cast<const T*>(cat), hw, cs, crop, w, mask_mode, leak, static_cast<T*>(dcat), part);
-    })
-  })
-  hipLaunchKernelGGL(cgan_head_finish_kernel, dim3(tdg_ceil_div(cin + 1, 256)), dim3(256), 0, (hipStream_t)stream, part, n, cin + 1,
-                     dw, db);
-  tdg_timing_stop((hipStream_t)stream);
-  TDG_HIP_LAUNCH_CHECK("cgan_head_bwd");
-  return TDG_OK;
+  return head_bwd("cgan_head_bwd", dtype, dfake, fake_cs, cat, n, hw, cin, cs, crop, w, nullptr, mask_mode, leak, dcat, dw, db,
+                  workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int tdg_cgan_head_noise_bwd(int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs,
+                                       int crop, const float* w, const float* u, int mask_mode, float leak, void* dcat, float* dw,
+                                       float* db, void* workspace, size_t workspace_bytes, void* stream) {
+  TDG_CHECK_ARG(dfake && cat && w && dcat && dw && db && workspace && n > 0 && crop > 0 && crop <= hw && cs >= cin && cs % 8 == 0 &&
+                    fake_cs > 0,
+                "tdg_cgan_head_noise_bwd: bad argument");
+  return head_bwd("cgan_head_noise_bwd", dtype, dfake, fake_cs, cat, n, hw, cin, cs, crop, w, u, mask_mode, leak, dcat, dw, db,
+                  workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int tdg_cgan_join(int dtype, int mode, int n_rgb, int rows, int c, void* comb, int comb_cs, void* rgb, int rgb_cs, void* depth,

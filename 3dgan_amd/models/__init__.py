@@ -18,7 +18,8 @@ def model_funcs():
             return train_func
         return func
     return {'gan': gan, 'wgan': gan, 'iwgan': gan, 'vae': vae, 'cnn': cnn, 'pix2pix': plugin_func('pix2pix'),
-            'paper_cgan': plugin_func('paper_cgan')}
+            'paper_cgan': plugin_func('paper_cgan'), 'paper_sampler': plugin_func('paper_sampler'),
+            'paper_noise': plugin_func('paper_noise')}
 
 
 def get_model(name):

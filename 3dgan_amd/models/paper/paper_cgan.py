@@ -50,27 +50,20 @@ METRIC_KEYS = ('abs_rel_diff', 'squared_rel_diff', 'linear_rmse', 'log_rmse', 's
                'threshold1', 'threshold2', 'threshold3')
 
 
-class paper_cgan(ModelPlugin, engine.Replica):
-    name = 'paper_cgan'
+class CganReplica(engine.Replica):
+    """What the thesis' depth cGAN plugins share (paper_cgan here, paper_sampler / paper_noise in models/sampler/): the
+    builders, the replica's buffers, the D and G steps, the Eigen metric sets and the dataset evaluation.  Not a
+    `ModelPlugin` subclass, so the plugin scan registers only the plugins themselves.  A plugin supplies `name`,
+    `arguments()` and `train()`, and may override `generator`."""
 
-    @staticmethod
-    def arguments():
-        """hem/models/paper_cgan.py:14-57."""
-        return {
-            '--g_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for generator.'},
-            '--d_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for discriminator.'},
-            '--g_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for generator'},
-            '--d_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for discriminator.'},
-            '--g_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for generator.'},
-            '--d_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for discriminator.'},
-            '--model_version': {'type': str, 'default': 'baseline',
-                                'choices': ['baseline', 'mean_adjusted', 'mean_provided', 'mean_provided2'],
-                                'help': 'Which version of the model to run.'},
-            '--training_version': {'type': str, 'default': 'gan', 'choices': ['gan', 'wgan'],
-                                   'help': 'Whether to use standard GAN training of Wasserstein GAN training.'},
-        }
+    NOISE_KEYS = None                # injection keys of the generator's noise nodes (unet.UNet's `noise_keys`)
 
     # ------------------------------------------------------------------------------ builders
+    @classmethod
+    def _version_name(cls, args):
+        """The row of the module docstring's table this plugin runs."""
+        return args.model_version
+
     @staticmethod
     def check_version(version):
         if version == 'mean_provided':
@@ -122,21 +115,21 @@ class paper_cgan(ModelPlugin, engine.Replica):
                 h = conv2d(h, 512, 1, stride=1, filter_size=1, padding='SAME', name='h3', activation=None)
         return h, h1, h2
 
-    @staticmethod
-    def build_graph(args):
+    @classmethod
+    def build_graph(cls, args):
         """Record both networks for `args` (no device work); returns the Nets by scope name."""
-        paper_cgan.check_version(args.model_version)
-        mp2 = args.model_version == 'mean_provided2'
+        cls.check_version(cls._version_name(args))
+        mp2 = cls._version_name(args) == 'mean_provided2'
         reset_graph()
         xs = placeholder((None, SRC, SRC, 3))
         gx = concat([xs, placeholder((None, SRC, SRC, 1), 'ones')]) if mp2 else xs
         rx = concat([xs, placeholder((None, SRC, SRC, 1), 'y_bar')]) if mp2 else xs
         dy = placeholder((None, CROP, CROP, 2 if mp2 else 1), 'y')
         with variable_scope('generator'):
-            paper_cgan.generator(gx, args)
+            cls.generator(gx, args)
         with variable_scope('discriminator'):
-            paper_cgan.discriminator(rx, dy, args, reuse=False)      # D(x, y_hat) first, as :123-136
-            paper_cgan.discriminator(rx, dy, args, reuse=True)
+            cls.discriminator(rx, dy, args, reuse=False)             # D(x, y_hat) first, as :123-136
+            cls.discriminator(rx, dy, args, reuse=True)
         from ...ops import layers as Lyr
         return {k: v for k, v in Lyr._nets.items() if v.passes}
 
@@ -146,12 +139,12 @@ class paper_cgan(ModelPlugin, engine.Replica):
     def __init__(self, x_y, args, sess=None):
         engine.Replica.__init__(self, args, sess)
         self.x_y, sess = x_y, self.sess
-        for flag, default in paper_cgan._defaults().items():
+        for flag, default in self._defaults().items():
             if not hasattr(args, flag):
                 setattr(args, flag, default)
-        self.check_version(args.model_version)
-        self.version = VERSIONS[args.model_version]
-        self.wgan = args.training_version == 'wgan'
+        self.check_version(self._version_name(args))
+        self.version = VERSIONS[self._version_name(args)]
+        self.wgan = getattr(args, 'training_version', 'gan') == 'wgan'
         B = self.B = args.batch_size
         dev, dt = sess.device, sess.dtype
         for _ in tower_scope_range(None, args.n_gpus, B, sess):
@@ -174,11 +167,13 @@ class paper_cgan(ModelPlugin, engine.Replica):
         # G input: D's rgb input where the two are the same tensor (baseline, mean_adjusted)
         self.gx = K.Act(B, SRC, SRC, 4, dt, dev) if mp2 else self.Dr.x
         # G: the U-Net hands over its last concat [d3 | e1]; the 1x1 head on the 29x29 crop is _generate / _g_backward
-        self.G = UNet(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx)
+        self.G = UNet(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx, sess=sess, noise_keys=self.NOISE_KEYS)
         self.head = self.dec_net.layers[-1]
-        if len(self.dec_net.layers) != self.G.nd + 1 or (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.G.top.c):
+        head_noise = 1 if self.G.head_u is not None else 0          # --noise_layer d4: the head reads its draw beside the concat
+        if len(self.dec_net.layers) != self.G.nd + 1 or \
+                (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.G.top.c + head_noise):
             raise ValueError('the generator head must be a 1x1 conv from the last concat to one channel')
-        self.head_ws = torch.zeros(B * (self.G.top.c + 1), dtype=torch.float32, device=dev)
+        self.head_ws = torch.zeros(B * (self.head.in_size + 1), dtype=torch.float32, device=dev)
         self.fake, self.dfake = self.Dd.x.view(B, B), self.Dd.dx.view(B, B)      # g lands in D's fake depth input
         self.d_store.allocate()
         self.g_store.allocate()
@@ -217,38 +212,47 @@ class paper_cgan(ModelPlugin, engine.Replica):
         self.eval_ws = torch.zeros(lib.tdg_cgan_eval_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.refresh()
 
-    @staticmethod
-    def _defaults():
-        return {k.lstrip('-'): v['default'] for k, v in paper_cgan.arguments().items()}
+    @classmethod
+    def _defaults(cls):
+        return {k.lstrip('-'): v['default'] for k, v in cls.arguments().items()}
 
     def _repack_d(self):
         for net in (self.Dr, self.Dd, self.Dc):
             net.repack()
 
     # ---- pieces ------------------------------------------------------------------------------------------
-    def _inputs(self, ybar, crop):
+    def _inputs(self, ybar, crop, x_src=None, y_src=None):
         """x into G's (and D's rgb) input, the depth target and the constant channels (:83-96, :286, :323, :326);
-        y_bar and the f32 crop into `ybar` / `crop`."""
+        y_bar and the f32 crop into `ybar` / `crop`.  x_src / y_src: f32 batches other than the staged one."""
         B, dt = self.B, self.sess.dtype
         rows = B * SRC * SRC
-        _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.Dr.x.cs, 1.0, 0.0, self.Dr.x.ptr(0), K.stream())
+        x = K.ptr(self.x_stage if x_src is None else x_src)
+        _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.Dr.x.cs, 1.0, 0.0, self.Dr.x.ptr(0), K.stream())
         if self.version == 2:
-            _lib.call('tdg_affine_cast_rows', dt, K.ptr(self.x_stage), rows, 3, self.gx.cs, 1.0, 0.0, self.gx.ptr(0), K.stream())
-        self._target(ybar, crop)
+            _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.gx.cs, 1.0, 0.0, self.gx.ptr(0), K.stream())
+        if self.G.xn is not None:                                # noise at x: the generator reads [x | noise] from its own buffer
+            _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.G.xn.cs, 1.0, 0.0, self.G.xn.ptr(0), K.stream())
+        self._target(ybar, crop, y_src)
 
-    def _target(self, ybar, crop):
+    def _target(self, ybar, crop, y_src=None):
         """The depth half of _inputs: the staged y into the depth target, y_bar and the f32 crop."""
         B, dt, mp2 = self.B, self.sess.dtype, self.version == 2
-        _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage), B, self.version, self.Dd.x.ptr(0), self.Dd.x.cs,
+        _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage if y_src is None else y_src), B, self.version, self.Dd.x.ptr(0), self.Dd.x.cs,
                   self.Dd.x.ptr(B) if mp2 else None, K.ptr(ybar), K.ptr(crop),
                   self.gx.window(3, 1).ptr(0) if mp2 else None, self.gx.cs,
                   self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs, K.stream())
 
-    def _generate(self, ybar, yhat):
+    def _generate(self, ybar, yhat, g32=None):
         """g (the cropped 1x1 head of the U-Net's last concat) into channel 0 of D's fake depth input, y_hat = g (+ y_bar,
-        :113-121) into `yhat` (f32)."""
+        :113-121) into `yhat` (f32).  g32: also g as f32 [B,29,29]; that, or a head with a noise channel, takes the head's
+        other entry point."""
         self.G.forward()
         c3, st, name = self.G.top, self.g_store, self.dec_net.var_name
+        if g32 is not None or self.G.head_u is not None:
+            _lib.call('tdg_cgan_head_noise_fwd', self.sess.dtype, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP,
+                      K.ptr(st[name(self.head, 'weights')]), K.ptr(st[name(self.head, 'bias')]), K.ptr(self.G.head_u),
+                      K.ptr(ybar if self.version != 0 else None), K.ptr(yhat), K.ptr(g32), self.fake.ptr(0), self.fake.cs, K.stream())
+            return
         _lib.call('tdg_cgan_head_fwd', self.sess.dtype, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP, K.ptr(st[name(self.head, 'weights')]),
                   K.ptr(st[name(self.head, 'bias')]), K.ptr(ybar if self.version != 0 else None), K.ptr(yhat), self.fake.ptr(0),
                   self.fake.cs, K.stream())
@@ -257,10 +261,16 @@ class paper_cgan(ModelPlugin, engine.Replica):
         """From dL/dg in channel 0 of D's fake depth-input gradient: the head writes the last concat's gradient
         [delta of d3 | dL/de1 from the skip] (the lrelu mask of d3 applied here, its producer), the U-Net takes it from there."""
         c3, gc3, st, name = self.G.top, self.G.gtop, self.g_store, self.dec_net.var_name
-        _lib.call('tdg_cgan_head_bwd', self.sess.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP,
-                  K.ptr(st[name(self.head, 'weights')]), K.MASK_LRELU, self.dec_net.layers[-2].act.leak, gc3.ptr(),
-                  K.ptr(st.grad(name(self.head, 'weights'))), K.ptr(st.grad(name(self.head, 'bias'))),
-                  K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
+        if self.G.head_u is not None:
+            _lib.call('tdg_cgan_head_noise_bwd', self.sess.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), self.B, c3.h, c3.c, c3.cs,
+                      CROP, K.ptr(st[name(self.head, 'weights')]), K.ptr(self.G.head_u), K.MASK_LRELU, self.dec_net.layers[-2].act.leak,
+                      gc3.ptr(), K.ptr(st.grad(name(self.head, 'weights'))), K.ptr(st.grad(name(self.head, 'bias'))),
+                      K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
+        else:
+            _lib.call('tdg_cgan_head_bwd', self.sess.dtype, self.dfake.ptr(0), self.dfake.cs, c3.ptr(), self.B, c3.h, c3.c, c3.cs, CROP,
+                      K.ptr(st[name(self.head, 'weights')]), K.MASK_LRELU, self.dec_net.layers[-2].act.leak, gc3.ptr(),
+                      K.ptr(st.grad(name(self.head, 'weights'))), K.ptr(st.grad(name(self.head, 'bias'))),
+                      K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
         self.G.backward()
 
     def _d_forward(self):
@@ -342,13 +352,6 @@ class paper_cgan(ModelPlugin, engine.Replica):
             items = [('loss/generator/g_fake', s[6]), ('loss/discriminator/d_fake', s[5]), ('loss/discriminator/d_real', s[4]),
                      ('loss/discriminator/d_total', s[4] + s[5])]
         return collection_to_dict([('tower_%d/%s:0' % (r, n), v) for n, v in items])
-
-    def train(self, sess=None, args=None, feed_dict=None):
-        """:200-209: gan -- one D step, then the G step and the loss fetch on the next batch; wgan -- five D steps first."""
-        for _ in range(5 if self.wgan else 1):
-            self.d_step(self.x_y.next_batch())
-        self.g_step(self.x_y.next_batch())
-        return self._losses()
 
     # ---- evaluation ----------------------------------------------------------------------------------------
     def metrics(self):
@@ -521,6 +524,34 @@ class paper_cgan(ModelPlugin, engine.Replica):
         self._generate(self.inf_ybar, self.inf_yhat)
         _lib.call('tdg_cgan_full_store', K.ptr(self.inf_yhat), K.ptr(self.inf_ybar) if self.version != 0 else None, self.B, fb.slots,
                   K.ptr(fb.chunk), K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), K.stream())
+
+
+class paper_cgan(ModelPlugin, CganReplica):
+    name = 'paper_cgan'
+
+    @staticmethod
+    def arguments():
+        """hem/models/paper_cgan.py:14-57."""
+        return {
+            '--g_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for generator.'},
+            '--d_lr': {'type': float, 'default': 1e-3, 'help': 'Learning rate for discriminator.'},
+            '--g_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for generator'},
+            '--d_beta1': {'type': float, 'default': 0.9, 'help': 'Beta1 for discriminator.'},
+            '--g_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for generator.'},
+            '--d_beta2': {'type': float, 'default': 0.999, 'help': 'Beta2 for discriminator.'},
+            '--model_version': {'type': str, 'default': 'baseline',
+                                'choices': ['baseline', 'mean_adjusted', 'mean_provided', 'mean_provided2'],
+                                'help': 'Which version of the model to run.'},
+            '--training_version': {'type': str, 'default': 'gan', 'choices': ['gan', 'wgan'],
+                                   'help': 'Whether to use standard GAN training of Wasserstein GAN training.'},
+        }
+
+    def train(self, sess=None, args=None, feed_dict=None):
+        """:200-209: gan -- one D step, then the G step and the loss fetch on the next batch; wgan -- five D steps first."""
+        for _ in range(5 if self.wgan else 1):
+            self.d_step(self.x_y.next_batch())
+        self.g_step(self.x_y.next_batch())
+        return self._losses()
 
 
 class _FullBuffers:

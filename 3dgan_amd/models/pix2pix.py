@@ -144,7 +144,8 @@ class pix2pix(ModelPlugin, engine.Replica):
         self.U = UNet(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws,
                       x_in=self.D.x.view(0, B).window(0, 3),
                       g_out=self.D.x.view(B, B).window(3, 1),
-                      g_grad=self.D.dx.view(B, B).window(3, 1), sess=sess)
+                      g_grad=self.D.dx.view(B, B).window(3, 1), sess=sess,
+                      noise_keys={'x': 'noise_input', 'e8': 'noise_latent', 'd8': 'noise_end'})
         self.d_store.allocate()
         self.g_store.allocate()
         gen = torch.Generator().manual_seed(sess.seed)

@@ -70,6 +70,7 @@ class LayerSpec:
         self.use_bn, self.act = use_bn, _resolve_activation(act, name)
         self.in_shape, self.out_shape = in_shape, out_shape
         self.padding, self.init = padding, init
+        self.noise = None                            # (channels, minval, maxval) of a random_uniform concatenated last onto the input
 
     def signature(self):
         return (self.kind, self.name, self.in_size, self.out_size, self.k, self.stride, self.use_bn,
@@ -251,6 +252,15 @@ def concat(xs, axis=-1):
     return out
 
 
+def _noise_part(x):
+    """(channels, minval, maxval) when `x` is a concat whose last part is a tf.random_uniform tensor, else None: the noise
+    channels the executor draws per pass (unet.py) and their range."""
+    parts = getattr(x, 'parts', None)
+    if parts and len(parts) > 1 and parts[-1].source == 'random_uniform':
+        return parts[-1].shape[-1], parts[-1].minval, parts[-1].maxval
+    return None
+
+
 def _same(in_size, k, stride):
     return -(-in_size // stride)
 
@@ -284,6 +294,7 @@ def conv2d(x, input_size, output_size, filter_size=3, stride=1, init='xavier', u
         oh, ow = -(-(h - filter_size + 1) // stride), -(-(w - filter_size + 1) // stride)
     spec = LayerSpec('conv2d', name, input_size, output_size, filter_size, stride, use_batch_norm, activation,
                      (h, w, c), (oh, ow, output_size), padding, init, use_in=use_in)
+    spec.noise = _noise_part(x)
     current_net().add(spec, reuse)
     return Sym((None, oh, ow, output_size), producer=spec)
 
@@ -337,5 +348,6 @@ def deconv2d(x, input_size, output_size, filter_size=3, stride=2, init='xavier',
                          % (name, padding, filter_size, stride, oh, ow, h, w))
     spec = LayerSpec('deconv2d', name, input_size, output_size, filter_size, stride, use_batch_norm, activation,
                      (h, w, c), (oh, ow, output_size), padding, init, dropout=dropout, use_in=use_in)
+    spec.noise = _noise_part(x)
     current_net().add(spec, reuse)
     return Sym((None, oh, ow, output_size), producer=spec)

@@ -33,10 +33,16 @@ def paper_model_plugins():
     return search_for_plugins(os.path.join(_HERE, 'models', 'paper'), '3dgan_amd.models.paper', 'ModelPlugin')
 
 
+def sampler_model_plugins():
+    """The thesis' noise / sampler experiment (hem/models/paper_sampler.py, paper_noise.py): `3dgan_amd/models/sampler/`."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'sampler'), '3dgan_amd.models.sampler', 'ModelPlugin')
+
+
 def all_model_plugins():
-    """Every `--model` plugin: both directories."""
+    """Every `--model` plugin: the three directories."""
     found = model_plugins()
     found.update(paper_model_plugins())
+    found.update(sampler_model_plugins())
     return found
 
 

@@ -13,9 +13,14 @@ shallower: the last concat and its gradient are handed to the caller as `top` / 
 the executed layers is the caller's head (paper_cgan); the caller's head writes `gtop` with the activation derivative of
 the last decoder layer already applied.
 
-`--noise input|latent|end` (a U(-1,1) channel concatenated to the generator input / the 1x1 bottleneck / the last decoder
-layer's input, hem/models/pix2pix.py:183-186,204-206,223-225) switches on from the recorded layer widths: each noise tensor
-is one more channel window, drawn per pass from the device Philox stream (keys 'noise_input', 'noise_latent', 'noise_end').
+Noise (pix2pix `--noise input|latent|end`, hem/models/pix2pix.py:183-186,204-206,223-225; paper_sampler `--noise_layer`,
+hem/models/paper_sampler.py:169-230) switches on from the recorded layer widths: a layer whose `in_size` is one more -- at the
+1x1 latent also: twice -- what its producers provide reads one more channel window, filled per pass with
+tf.random_uniform(minval, maxval) of the recorded draw (`spec.noise`) from the device Philox stream.  The nodes are 'x' (the
+generator input), 'e1' .. 'e<n>' (behind that encoder output; 'e<n>' is the latent) and 'd2' .. 'd<n>' (behind that decoder
+layer's skip concat); the injection key of a node is 'noise_<node>' unless `noise_keys` names another.  Every concat stays
+zero-copy -- the layouts are in UNet's docstring.  A head of the caller's that reads a noise channel ('d<n>' without `g_out`)
+gets its f32 draw in `head_u`; the concat is not widened for it.
 Dropout (`spec.dropout` = keep probability, hem/ops/layers.py:207) runs on the decoder layers that record it.
 """
 import torch
@@ -32,11 +37,17 @@ class UNet:
     writes its activation into the right window of cat[n+1-k] and receives its gradient -- skip path first, main path
     accumulated on top -- in the right window of gcat[n+1-k].
 
+    Noise windows.  cat[i] is allocated as [d | e | noise] when either of its readers takes a noise channel: decoder layer i
+    ('d<i>') reads all cd + ce + 1 channels and the next encoder layer its own window (cd, ce); with 'e<k>' the next encoder
+    layer reads the window (cd, ce + 1) and decoder layer i the window (0, cd + ce).  cd is a multiple of 8, so every window
+    starts on a 16-byte boundary.  The backward-data GEMM of the noise's reader also writes a gradient for the noise
+    channel; nothing reads it.  The latent is [e_n | noise] of 1 or e_n's width channels, the input [x | noise].
+
     Gradient bookkeeping as in engine.SeqNet: a layer with batch norm keeps its normalised pre-activation and a delta buffer
     of its own; a layer without has delta == the gradient of its output, because the GEMM that produces that gradient
     applies the (l)relu derivative in its epilogue."""
 
-    def __init__(self, enet, dnet, B, dtype, device, store, ws, x_in, g_out=None, g_grad=None, sess=None):
+    def __init__(self, enet, dnet, B, dtype, device, store, ws, x_in, g_out=None, g_grad=None, sess=None, noise_keys=None):
         self.B, self.dtype, self.device, self.store, self.ws = B, dtype, device, store, ws
         self.sess = sess
         self.enet, self.dnet = enet, dnet
@@ -50,22 +61,48 @@ class UNet:
                 raise NotImplementedError('layer %s: without batch norm only relu / lrelu (the derivative mask of the GEMM epilogue)' % spec.name)
         A = lambda h, w, c: K.Act(B, h, w, c, dtype, device)
         H, W = E[0].in_shape[:2]
-        self.noise_input = E[0].in_size == x_in.c + 1
-        self.noise_latent = Dc[0].in_size == 2 * E[n - 1].out_size
-        self.noise_end = g_out is not None and Dc[n - 1].in_size == Dc[n - 2].out_size + E[0].out_size + 1
-        self.xn = A(H, W, x_in.c + 1) if self.noise_input else None
-        if self.noise_input:
+        # noise channels each layer reads behind what its producers provide
+        self.noise_ch = {}                         # node -> channels
+
+        def extra(node, spec, provided, allowed=(0, 1)):
+            ch = spec.in_size - provided
+            if ch not in allowed:
+                raise ValueError('layer %s expects %d input channels, its producers provide %d' % (spec.name, spec.in_size, provided))
+            if ch and (spec.noise is None or spec.noise[0] != ch):
+                raise ValueError('layer %s reads %d channels more than its producers provide, and they are no recorded '
+                                 'random_uniform draw' % (spec.name, ch))
+            if ch:
+                self.noise_ch[node] = ch
+            return ch
+        extra('x', E[0], x_in.c)
+        for k in range(1, n):
+            extra('e%d' % k, E[k], E[k - 1].out_size)
+        extra('e%d' % n, Dc[0], E[n - 1].out_size, (0, 1, E[n - 1].out_size))
+        for i in range(2, n + 1):
+            extra('d%d' % i, Dc[i - 1], Dc[i - 2].out_size + E[n - i].out_size)
+        self.xn = A(H, W, x_in.c + 1) if 'x' in self.noise_ch else None
+        if self.xn is not None:
             x_in = self.xn
         self.x_in = x_in
-        self.cat, self.gcat = {}, {}
+        # cat[i]: the buffer; cat_in[i]: what decoder layer i reads of it; wide[i]: [e | noise], what encoder layer n + 2 - i reads
+        self.cat, self.gcat, self.cat_in, self.gcat_in, self.wide, self.gwide = {}, {}, {}, {}, {}, {}
+        noise_at = {}
         for i in range(2, n + 1):
             cd, ce = Dc[i - 2].out_size, E[n - i].out_size
-            extra = 1 if (i == n and self.noise_end) else 0
-            if Dc[i - 1].in_size != cd + ce + extra:
-                raise ValueError('decoder layer %d expects %d input channels, skip concat provides %d' % (i, Dc[i - 1].in_size, cd + ce + extra))
+            dn = 'd%d' % i in self.noise_ch and i <= nd          # (a caller's head reads its own draw)
+            en = 'e%d' % (n + 1 - i) in self.noise_ch
+            if dn and en:
+                raise NotImplementedError('noise both behind encoder layer %d and behind its skip concat' % (n + 1 - i))
             h, w = E[n - i].out_shape[:2]
-            self.cat[i], self.gcat[i] = A(h, w, cd + ce + extra), A(h, w, cd + ce + extra)
-        self.top, self.gtop = (self.cat[n], self.gcat[n]) if g_out is None else (None, None)
+            c = cd + ce + (1 if dn or en else 0)
+            self.cat[i], self.gcat[i] = A(h, w, c), A(h, w, c)
+            self.cat_in[i], self.gcat_in[i] = (self.cat[i].window(0, cd + ce), self.gcat[i].window(0, cd + ce)) if en else \
+                (self.cat[i], self.gcat[i])
+            if en:
+                self.wide[i], self.gwide[i] = self.cat[i].window(cd, ce + 1), self.gcat[i].window(cd, ce + 1)
+            if dn or en:
+                noise_at['d%d' % i if dn else 'e%d' % (n + 1 - i)] = self.cat[i].window(cd + ce, 1)
+        self.top, self.gtop = (self.cat_in[n], self.gcat_in[n]) if g_out is None else (None, None)
         # encoder activations / gradients
         self.e_h, self.e_g, self.e_pre, self.e_delta, self.e_stats, self.e_bn_name = {}, {}, {}, {}, {}, {}
         for k in range(1, n + 1):
@@ -75,9 +112,11 @@ class UNet:
                 cd = Dc[n - 1 - k].out_size
                 self.e_h[k] = self.cat[n + 1 - k].window(cd, co)
                 self.e_g[k] = self.gcat[n + 1 - k].window(cd, co)     # dL/d(e_k output); == delta when no batch norm
-            elif self.noise_latent:                # [e_n | noise]: e_n is the left window of decoder layer 1's input
-                self.lat, self.glat = A(h, w, 2 * co), A(h, w, 2 * co)
+            elif 'e%d' % n in self.noise_ch:       # [e_n | noise]: e_n is the left window of decoder layer 1's input
+                lc = co + self.noise_ch['e%d' % n]
+                self.lat, self.glat = A(h, w, lc), A(h, w, lc)
                 self.e_h[k], self.e_g[k] = self.lat.window(0, co), self.glat.window(0, co)
+                noise_at['e%d' % n] = self.lat.window(co, lc - co)
             else:
                 self.e_h[k], self.e_g[k] = A(h, w, co), A(h, w, co)
             if spec.use_bn:
@@ -101,15 +140,17 @@ class UNet:
                 self.d_bn_name[i] = dnet.bn_name(0, i - 1)
             else:
                 self.d_delta[i] = self.d_g[i]
-                if i < n and (E[n - i - 1].use_bn or E[n - i - 1].act.code != K.ACT_RELU):
+                if i < n and (E[n - i - 1].act is None or E[n - i - 1].act.code != K.ACT_RELU):
                     # the GEMM that writes gcat[i + 1] masks BOTH windows with act'(cat[i + 1]); on e's window that is only
-                    # harmless when e's own relu mask, applied on top of the accumulated main path, zeroes whatever it scaled
-                    raise NotImplementedError('decoder layer %s without batch norm beside an encoder layer that is not a plain relu' % spec.name)
+                    # harmless when e's own relu mask zeroes whatever it scaled: where e > 0 the factor is 1, and where e == 0
+                    # the relu derivative -- the epilogue mask on top of the accumulated main path, or the one inside the
+                    # batch-norm backward pass -- zeroes the entry
+                    raise NotImplementedError('decoder layer %s without batch norm beside an encoder layer that is not a relu' % spec.name)
         # convs (descriptors carry the strides of the buffers each GEMM form touches)
         self.e_conv, self.d_conv = {}, {}
         for k in range(1, n + 1):
             spec = E[k - 1]
-            big = self.x_in if k == 1 else self.e_h[k - 1]
+            big = self._e_in(k)
             small = self.e_pre[k] if spec.use_bn else self.e_h[k]
             self.e_conv[k] = K.Conv(big, small, spec.k, spec.k, spec.stride, *engine.conv_pads(spec, big, small))
         for i in range(1, nd + 1):
@@ -121,15 +162,29 @@ class UNet:
         self.d_keep = {i: float(getattr(Dc[i - 1], 'dropout', 0) or 0) for i in range(1, nd + 1)}
         self.d_u = {i: torch.zeros(B * self.d_h[i].h * self.d_h[i].w * Dc[i - 1].out_size, dtype=torch.float32, device=device)
                     for i in range(1, nd + 1) if self.d_keep[i] > 0}
-        # noise channel windows and the f32 staging of their uniform draws
-        self.noise = {}
-        if self.noise_input:
-            self.noise['noise_input'] = self.xn.window(x_in.c - 1, 1)
-        if self.noise_latent:
-            self.noise['noise_latent'] = self.lat.window(E[n - 1].out_size, E[n - 1].out_size)
-        if self.noise_end:
-            self.noise['noise_end'] = self.cat[n].window(Dc[n - 1].in_size - 1, 1)
-        self.noise_u = {k: torch.zeros(B * a.h * a.w * a.c, dtype=torch.float32, device=device) for k, a in self.noise.items()}
+        # noise channel windows in node order ('x', 'e1' .., 'd2' ..: the order of the draws), each with the f32 staging of its
+        # uniform draw and the affine map of tdg_affine_cast_rows that turns U(0,1) into U(minval, maxval)
+        if self.xn is not None:
+            noise_at['x'] = self.xn.window(self.xn.c - 1, 1)
+        reader = dict([('x', E[0])] + [('e%d' % k, E[k]) for k in range(1, n)] + [('e%d' % n, Dc[0])] +
+                      [('d%d' % i, Dc[i - 1]) for i in range(2, n + 1)])
+        self.noise, self.noise_map, self.head_u = {}, {}, None
+        for node in reader:
+            if node not in self.noise_ch:
+                continue
+            key = (noise_keys or {}).get(node, 'noise_' + node)
+            _, lo, hi = reader[node].noise
+            if node in noise_at:
+                self.noise[key], self.noise_map[key] = noise_at[node], (hi - lo, lo / (hi - lo))
+            elif (lo, hi) != (0.0, 1.0):
+                raise NotImplementedError("the head's noise channel is read as drawn: U(0,1), not U(%g,%g)" % (lo, hi))
+            else:                                  # the caller's head: the f32 draw [B, h, w] itself
+                self.noise[key] = None
+        self.noise_u = {k: torch.zeros(B * (a.h * a.w * a.c if a is not None else self.top.h * self.top.w), dtype=torch.float32,
+                                       device=device) for k, a in self.noise.items()}
+        for k, a in self.noise.items():
+            if a is None:
+                self.head_u = self.noise_u[k]
         # variables: every recorded layer of both nets (a caller's head included), batch-norm betas beside their layer
         for net, bn_names in ((enet, self.e_bn_name), (dnet, self.d_bn_name)):
             for idx, spec in enumerate(net.layers):
@@ -156,17 +211,30 @@ class UNet:
         K.pack_all(self._pack_jobs)
 
     def _d_in(self, i):
-        """Input tensor of decoder layer i: [e_n (| noise)] for i = 1, the skip concat otherwise."""
+        """Input tensor of decoder layer i: [e_n (| noise)] for i = 1, the skip concat (| noise) otherwise."""
         if i > 1:
-            return self.cat[i]
-        return self.lat if self.noise_latent else self.e_h[self.n]
+            return self.cat_in[i]
+        return self.lat if 'e%d' % self.n in self.noise_ch else self.e_h[self.n]
+
+    def _e_in(self, k):
+        """Input tensor of encoder layer k: x (| noise) for k = 1, e_{k-1} (| noise) otherwise."""
+        if k == 1:
+            return self.x_in
+        return self.wide.get(self.n + 2 - k, self.e_h[k - 1])
+
+    def _e_gin(self, k):
+        """Where encoder layer k's backward-data GEMM delivers its gradient: e_{k-1}'s window (| the unread noise gradient)."""
+        return self.gwide.get(self.n + 2 - k, self.e_g[k - 1])
 
     def draw_noise(self):
-        """tf.random_uniform(minval=-1, maxval=1) into every noise window (one draw per generator pass, as in TF)."""
+        """tf.random_uniform(minval, maxval) into every noise window (one draw per generator pass, as in TF)."""
         for key, a in self.noise.items():
             u = self.noise_u[key]
             self.sess.random_uniform(u, u.numel(), key)
-            _lib.call('tdg_affine_cast_rows', self.dtype, K.ptr(u), self.B * a.h * a.w, a.c, a.cs, 2.0, -0.5, a.ptr(0), K.stream())
+            if a is not None:
+                scale, shift = self.noise_map[key]
+                _lib.call('tdg_affine_cast_rows', self.dtype, K.ptr(u), self.B * a.h * a.w, a.c, a.cs, scale, shift, a.ptr(0),
+                          K.stream())
 
     # ---- forward: the last executed decoder layer's output into g_out / the left window of `top` ------------------
     def forward(self, backward_follows=True):
@@ -177,7 +245,7 @@ class UNet:
         self.draw_noise()
         for k in range(1, self.n + 1):
             spec = self.enet.layers[k - 1]
-            src = self.x_in if k == 1 else self.e_h[k - 1]
+            src = self._e_in(k)
             self._layer_fwd(self.e_conv[k].fwd, src, spec, self._var(self.enet, spec, 'bias'), self.e_pre.get(k), self.e_h[k],
                             self.e_bn_name.get(k), self.e_stats.get(k))
         for i in range(1, self.nd + 1):
@@ -219,17 +287,16 @@ class UNet:
                                       self.d_stats.get(i))
             conv.bwd_filter(delta.ptr(), self._d_in(i).ptr(), self._grad(self.dnet, spec, 'weights'), B, 0.0)
             if i > 1:                                                             # first writer of gcat[i] (both windows)
-                conv.fwd(delta.ptr(), self.gcat[i].ptr(), B, self._into_decoder(i - 1))
+                conv.fwd(delta.ptr(), self.gcat_in[i].ptr(), B, self._into_decoder(i - 1))
             else:
                 conv.fwd(delta.ptr(), self.e_g[self.n].ptr(), B, self._into_encoder(self.n, accumulate=False))
         for k in range(self.n, 0, -1):
             spec, conv = self.enet.layers[k - 1], self.e_conv[k]
             delta = self._layer_delta(self.enet, spec, self.e_g[k], self.e_pre.get(k), self.e_delta[k], self.e_bn_name.get(k),
                                       self.e_stats.get(k))
-            src = self.x_in if k == 1 else self.e_h[k - 1]
-            conv.bwd_filter(src.ptr(), delta.ptr(), self._grad(self.enet, spec, 'weights'), B, 0.0)
+            conv.bwd_filter(self._e_in(k).ptr(), delta.ptr(), self._grad(self.enet, spec, 'weights'), B, 0.0)
             if k > 1:
-                conv.bwd_data(delta.ptr(), self.e_g[k - 1].ptr(), B, self._into_encoder(k - 1, accumulate=True))
+                conv.bwd_data(delta.ptr(), self._e_gin(k).ptr(), B, self._into_encoder(k - 1, accumulate=True))
 
     def _layer_delta(self, net, spec, g, pre, delta, bn_name, stats):
         """dL/d(conv output incl. bias) of one layer and its bias gradient: batch norm's backward pass gives both; without

@@ -291,6 +291,17 @@ int tdg_cgan_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs
 int tdg_cgan_head_bwd(int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs, int crop,
                       const float* w, int mask_mode, float leak, void* dcat, float* dw, float* db, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* tdg_cgan_head_noise_fwd / _bwd: the head of paper_sampler --noise_layer d4, a (cin + 1) -> 1 conv whose last input channel is
+ * a uniform draw (hem/models/paper_sampler.py:228-230).  The concat is not widened: u f32 [n,hw,hw] is read directly,
+ *   g = w[0:cin] . cat + w[cin] * u + b,   dw[cin] = sum_p delta[p] * u[p]  (w and dw hold cin + 1 entries; workspace of
+ *   n * (cin + 2) floats, the same per-image partials finished in image order); no gradient goes to u.
+ * u nullable: then exactly tdg_cgan_head_fwd / _bwd (w and dw of cin entries, n * (cin + 1) floats), bit for bit.
+ * g (nullable): g as f32 [n,crop,crop], before its rounding into `fake` (the sampler statistics read it). */
+int tdg_cgan_head_noise_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w, const float* b,
+                            const float* u, const float* ybar, float* yhat, float* g, void* fake, int fake_cs, void* stream);
+int tdg_cgan_head_noise_bwd(int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs, int crop,
+                            const float* w, const float* u, int mask_mode, float leak, void* dcat, float* dw, float* db,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* tdg_cgan_join: D's combined input [rows, comb_cs] = [rgb path output | depth path output] (:332) where the rgb path ran
  * ONCE over n_rgb images (it is the same for D(x,y) and D(x,yhat)) and the depth path over both halves.
  *   mode 0: comb[r, 0:c] = rgb[r % n_rgb], comb[r, c:2c] = depth[r]                                   (r < rows)
@@ -335,6 +346,18 @@ size_t tdg_cgan_eval_acc_bytes(int hw);
 /* tdg_cgan_eval_moments: tf.nn.moments(y, axes=0) of y f32 [n,hw] in float64, two passes: per pixel the batch mean and the mean
  *   of the squared deviations from it, added to acc[28 + p] and acc[28 + hw + p]; acc[27] += 1. */
 int tdg_cgan_eval_moments(const float* y, int n, int hw, double* acc, void* stream);
+/* tdg_cgan_sample_stats: what paper_sampler's metric_summaries adds to the eight Eigen values (hem/models/paper_sampler.py:337-342)
+ *   for one set of n images of hw pixels.  y f32 [n,hw]; g f32 [n,hw] (nullable: 0); the prediction as tdg_cgan_eval_batch takes
+ *   it: y_hat[b,p] = image[p] * image_scale (image given; pred and offset must be null) or pred[b,p] + offset[b] (either
+ *   nullable: 0), rounded in f32; everything after that in f64.  out f32 [6], in units of `unit` (10: the reference's [0,1]):
+ *   [0], [1] the mean and the min over the images of mean_p |y - y_hat| / unit;  [2], [3] the mean over the pixels of the
+ *   batch mean of g / unit and of its population variance / unit^2 (tf.nn.moments(g, axes=0), two passes);  [4], [5] the same
+ *   of y_hat.  mean_img / var_img (both or neither) f32 [hw]: the per-pixel batch mean / unit and variance / unit^2 of y_hat.
+ *   Fixed-order f64 reductions (no atomics): two launches are bit-equal. */
+int tdg_cgan_sample_stats(const float* y, const float* g, const float* pred, const float* offset, const float* image,
+                          float image_scale, int n, int hw, float unit, float* out, float* mean_img, float* var_img,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t tdg_cgan_sample_stats_workspace_bytes(int n, int hw);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */
