@@ -107,6 +107,9 @@ SIGNATURES = {
     'tdg_cgan_eval_finish': (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     'tdg_cgan_sample_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_sample_stats_workspace_bytes': (_sz, [_i, _i]),
+    'tdg_cgan_rmse_loss': (_i, [_i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_rmse_loss_workspace_bytes': (_sz, [_i, _i]),
+    'tdg_cgan_bar_fill': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

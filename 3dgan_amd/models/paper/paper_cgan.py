@@ -24,6 +24,9 @@ Dataset evaluation (paper/paper_metrics.py, the mean / variance image pre-pass o
 `metrics_y_mean`, :79,177): set_mean_image / dataset_moments / evaluate on the kernels of tdg_cgan_eval.hip; a sweep adds
 every batch into device-resident f64 accumulators and reads the host once.
 
+Classes: GeneratorReplica is everything here that needs no critic (the generator, its pass and backward pass, metrics, dataset
+evaluation, full-frame inference; models/standalone/ trains it on a regression loss), CganReplica the critic on top of it.
+
 MI355X-native: activations are NHWC; the generator runs on the skip U-Net executor (unet.py: zero-copy skip concats);
 D's rgb path runs ONCE over the B images -- it is identical for D(x, y) and D(x, y_hat) -- and its output fills the left
 window of both halves of the combined input (tdg_cgan_join), its backward sums the two halves' gradients first; the depth
@@ -42,6 +45,7 @@ from ...util import tower_scope_range, collection_to_dict
 from ..ModelPlugin import ModelPlugin
 
 VERSIONS = {'baseline': 0, 'mean_adjusted': 1, 'mean_provided2': 2}
+PREP_VERSION = (0, 1, 2, 1)     # tdg_cgan_prep's version per version code: 3 (y_bar fed behind e1) has mean_adjusted's target
 SRC, CROP = 65, 29
 FULL_OFFSET = 18                 # paper_fullimage.py:138 places the 29x29 output at +18 (training crops the target at +17)
 FULL_MIN_SIDE = SRC + CROP       # 94: the smallest frame side with one window
@@ -50,13 +54,16 @@ METRIC_KEYS = ('abs_rel_diff', 'squared_rel_diff', 'linear_rmse', 'log_rmse', 's
                'threshold1', 'threshold2', 'threshold3')
 
 
-class CganReplica(engine.Replica):
-    """What the thesis' depth cGAN plugins share (paper_cgan here, paper_sampler / paper_noise in models/sampler/): the
-    builders, the replica's buffers, the D and G steps, the Eigen metric sets and the dataset evaluation.  Not a
-    `ModelPlugin` subclass, so the plugin scan registers only the plugins themselves.  A plugin supplies `name`,
-    `arguments()` and `train()`, and may override `generator`."""
+class GeneratorReplica(engine.Replica):
+    """The generator half of the thesis' depth plugins, with no critic: the generator builders, the replica's buffers, the
+    generator pass and its backward pass from dL/dg, the Eigen metric sets, the dataset evaluation and the full-frame
+    inference.  paper_standalone / paper_baseline_standalone (models/standalone/) train it on a regression loss; CganReplica
+    puts the critic on top.  Without a critic g and dL/dg live in two small buffers of the replica's own, and tdg_cgan_prep
+    writes its depth target into a scratch buffer.  Not a `ModelPlugin` subclass, so the plugin scan registers only the
+    plugins themselves.  A plugin supplies `name`, `arguments()` and `train()`, and may override `generator`."""
 
     NOISE_KEYS = None                # injection keys of the generator's noise nodes (unet.UNet's `noise_keys`)
+    VERSIONS = VERSIONS              # --model_version -> code; 3 (models/standalone/): mean_adjusted's target, y_bar fed behind e1
 
     # ------------------------------------------------------------------------------ builders
     @classmethod
@@ -64,8 +71,8 @@ class CganReplica(engine.Replica):
         """The row of the module docstring's table this plugin runs."""
         return args.model_version
 
-    @staticmethod
-    def check_version(version):
+    @classmethod
+    def check_version(cls, version):
         if version == 'mean_provided':
             raise ValueError("paper_cgan --model_version mean_provided cannot be built: the reference's g_mean_provided "
                              "calls tf.variablpe_scope (hem/models/paper_cgan.py:245) and raises AttributeError")
@@ -94,48 +101,25 @@ class CganReplica(engine.Replica):
             y = conv2d(y, 128, 1, stride=1, filter_size=1, padding='SAME', activation=None, name='d4')   # 31x31x1
         return y, (c1, c2, c3)
 
-    @staticmethod
-    def discriminator(x, y, args, reuse=False):
-        """d_baseline (:312-338) / d_mean_provided2 (:362-388, x and y already carry their y_bar channel).
-        Returns the logits [B,1,1,1] and the two path outputs."""
-        with arg_scope([conv2d], reuse=reuse, activation=_lrelu(0.2), init='xavier', padding='VALID', filter_size=5, stride=2):
-            with variable_scope('rgb_path'):
-                h1 = conv2d(x, x.shape[-1], 64, name='hx1')     # 31x31x64
-                h1 = conv2d(h1, 64, 128, name='hx2')            # 14x14x128
-                h1 = conv2d(h1, 128, 256, name='hx3')           # 5x5x256
-                h1 = conv2d(h1, 256, 512, name='hx4')           # 1x1x512
-            with variable_scope('depth_path'):
-                h2 = conv2d(y, y.shape[-1], 128, name='hy1')    # 13x13x128 (the reference's "14x14" comment at :326 is off)
-                h2 = conv2d(h2, 128, 256, name='hy2')           # 5x5x256
-                h2 = conv2d(h2, 256, 512, name='hy3')           # 1x1x512
-            with variable_scope('combined_path'):
-                h = concat([h1, h2])                            # 1x1x1024
-                h = conv2d(h, 1024, 1024, stride=1, filter_size=1, padding='SAME', name='h1')
-                h = conv2d(h, 1024, 512, stride=1, filter_size=1, padding='SAME', name='h2')
-                h = conv2d(h, 512, 1, stride=1, filter_size=1, padding='SAME', name='h3', activation=None)
-        return h, h1, h2
+    @classmethod
+    def record_critic(cls, xs, args, mp2):
+        """The critic's networks behind the generator's, for the plugins that have one."""
 
     @classmethod
     def build_graph(cls, args):
-        """Record both networks for `args` (no device work); returns the Nets by scope name."""
+        """Record the networks for `args` (no device work); returns the Nets by scope name."""
         cls.check_version(cls._version_name(args))
         mp2 = cls._version_name(args) == 'mean_provided2'
         reset_graph()
         xs = placeholder((None, SRC, SRC, 3))
         gx = concat([xs, placeholder((None, SRC, SRC, 1), 'ones')]) if mp2 else xs
-        rx = concat([xs, placeholder((None, SRC, SRC, 1), 'y_bar')]) if mp2 else xs
-        dy = placeholder((None, CROP, CROP, 2 if mp2 else 1), 'y')
         with variable_scope('generator'):
             cls.generator(gx, args)
-        with variable_scope('discriminator'):
-            cls.discriminator(rx, dy, args, reuse=False)             # D(x, y_hat) first, as :123-136
-            cls.discriminator(rx, dy, args, reuse=True)
+        cls.record_critic(xs, args, mp2)
         from ...ops import layers as Lyr
         return {k: v for k, v in Lyr._nets.items() if v.passes}
 
     # ------------------------------------------------------------------------------ construction
-    S_GFAKE, S_DFAKE, S_DREAL, S_DTOTAL = 0, 1, 2, 3
-
     def __init__(self, x_y, args, sess=None):
         engine.Replica.__init__(self, args, sess)
         self.x_y, sess = x_y, self.sess
@@ -143,52 +127,32 @@ class CganReplica(engine.Replica):
             if not hasattr(args, flag):
                 setattr(args, flag, default)
         self.check_version(self._version_name(args))
-        self.version = VERSIONS[self._version_name(args)]
-        self.wgan = getattr(args, 'training_version', 'gan') == 'wgan'
+        self.version = self.VERSIONS[self._version_name(args)]
         B = self.B = args.batch_size
         dev, dt = sess.device, sess.dtype
         for _ in tower_scope_range(None, args.n_gpus, B, sess):
             nets = self.build_graph(args)
         self.enet, self.dec_net = nets['generator/encoder'], nets['generator/decoder']
-        rgb_net, depth_net, comb_net = (nets['discriminator/' + s] for s in ('rgb_path', 'depth_path', 'combined_path'))
 
         self.ws = K.Workspace(dev)
-        self.g_store, self.d_store = engine.ParamStore(dev), engine.ParamStore(dev)
+        self.g_store = engine.ParamStore(dev)
         mp2 = self.version == 2
-        # D: combined path over 2B (images [0,B) real, [B,2B) fake), depth path over 2B, rgb path over B
-        self.Dc = engine.SeqNet(comb_net, 2 * B, (1, 1, 1024), dt, dev, self.d_store, need_input_grad=True, ws=self.ws)
-        self.Dr = engine.SeqNet(rgb_net, B, (SRC, SRC, 4 if mp2 else 3), dt, dev, self.d_store, ws=self.ws)
-        self.Dd = engine.SeqNet(depth_net, 2 * B, (CROP, CROP, 2 if mp2 else 1), dt, dev, self.d_store, need_input_grad=True,
-                                ws=self.ws)
-        for net in (self.Dr, self.Dd, self.Dc):
-            net.declare_variables()
-        self.rgb_g = self.Dr.layers[-1].gout                 # dL/d(rgb path output): both halves summed by tdg_cgan_join
-        self.depth_g = self.Dd.layers[-1].gout
+        self.rgb_x = self._build_critic(nets, args)          # the critic's rgb input (None: no critic)
         # G input: D's rgb input where the two are the same tensor (baseline, mean_adjusted)
-        self.gx = K.Act(B, SRC, SRC, 4, dt, dev) if mp2 else self.Dr.x
+        self.gx = K.Act(B, SRC, SRC, 4, dt, dev) if mp2 else (K.Act(B, SRC, SRC, 3, dt, dev) if self.rgb_x is None else self.rgb_x)
         # G: the U-Net hands over its last concat [d3 | e1]; the 1x1 head on the 29x29 crop is _generate / _g_backward
         self.G = UNet(self.enet, self.dec_net, B, dt, dev, self.g_store, self.ws, self.gx, sess=sess, noise_keys=self.NOISE_KEYS)
         self.head = self.dec_net.layers[-1]
-        head_noise = 1 if self.G.head_u is not None else 0          # --noise_layer d4: the head reads its draw beside the concat
+        head_noise = 1 if self.G.head_u is not None else 0          # the head reads its draw / fed plane beside the concat
         if len(self.dec_net.layers) != self.G.nd + 1 or \
                 (self.head.k, self.head.out_size, self.head.in_size) != (1, 1, self.G.top.c + head_noise):
             raise ValueError('the generator head must be a 1x1 conv from the last concat to one channel')
         self.head_ws = torch.zeros(B * (self.head.in_size + 1), dtype=torch.float32, device=dev)
-        self.fake, self.dfake = self.Dd.x.view(B, B), self.Dd.dx.view(B, B)      # g lands in D's fake depth input
-        self.d_store.allocate()
-        self.g_store.allocate()
+        self.fake, self.dfake = self._g_buffers()
+        self._allocate()
         gen = torch.Generator().manual_seed(sess.seed)
         self.G.init_variables(gen)
-        for net in (self.Dr, self.Dd, self.Dc):
-            net.init_variables(gen)
-        if self.wgan:                                        # :64-66
-            self.g_opt = engine.RMSProp(self.g_store, args.g_lr, decay=0.9, momentum=0.0, eps=1e-10)
-            self.d_opt = engine.Adam(self.d_store, args.d_lr)
-        else:                                                # :67-69
-            self.g_opt = engine.Adam(self.g_store, args.g_lr, args.g_beta1, args.g_beta2)
-            self.d_opt = engine.Adam(self.d_store, args.d_lr, args.d_beta1, args.d_beta2)
-        self.register('generator', self.g_store, self.g_opt, self.G.repack)
-        self.register('discriminator', self.d_store, self.d_opt, self._repack_d)
+        self._setup(args, gen)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.x_stage, self.y_stage = self.staging((B, SRC, SRC, 3), (B, SRC, SRC, 1))
         self.ybar, self.crop, self.yhat = f32(B), f32(B, CROP, CROP), f32(B, CROP, CROP)     # of the last loss fetch
@@ -216,9 +180,27 @@ class CganReplica(engine.Replica):
     def _defaults(cls):
         return {k.lstrip('-'): v['default'] for k, v in cls.arguments().items()}
 
-    def _repack_d(self):
-        for net in (self.Dr, self.Dd, self.Dc):
-            net.repack()
+    # ---- what a critic changes (CganReplica) -----------------------------------------------------------------
+    def _build_critic(self, nets, args):
+        """No critic: tdg_cgan_prep's depth target goes to a scratch buffer that nothing reads."""
+        self.prep_scratch = K.Act(self.B, CROP, CROP, 2 if self.version == 2 else 1, self.sess.dtype, self.sess.device)
+        return None
+
+    def _g_buffers(self):
+        """Where g lands and where dL/dg is read from, channel 0 of each: two small buffers of the replica's own."""
+        B, dt, dev = self.B, self.sess.dtype, self.sess.device
+        return K.Act(B, CROP, CROP, 1, dt, dev), K.Act(B, CROP, CROP, 1, dt, dev)
+
+    def _allocate(self):
+        self.g_store.allocate()
+
+    def _setup(self, args, gen):
+        """After the generator's variables are initialised from `gen`: further variables, the optimizers, register()."""
+        raise NotImplementedError
+
+    def _prep_targets(self):
+        """tdg_cgan_prep's device targets: (depth_real, its channel stride, depth_fake, rgb y_bar channel, its stride)."""
+        return self.prep_scratch.ptr(0), self.prep_scratch.cs, self.fake.ptr(0) if self.version == 2 else None, None, 0
 
     # ---- pieces ------------------------------------------------------------------------------------------
     def _inputs(self, ybar, crop, x_src=None, y_src=None):
@@ -227,20 +209,23 @@ class CganReplica(engine.Replica):
         B, dt = self.B, self.sess.dtype
         rows = B * SRC * SRC
         x = K.ptr(self.x_stage if x_src is None else x_src)
-        _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.Dr.x.cs, 1.0, 0.0, self.Dr.x.ptr(0), K.stream())
-        if self.version == 2:
+        if self.rgb_x is not None:
+            _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.rgb_x.cs, 1.0, 0.0, self.rgb_x.ptr(0), K.stream())
+        if self.gx is not self.rgb_x:
             _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.gx.cs, 1.0, 0.0, self.gx.ptr(0), K.stream())
         if self.G.xn is not None:                                # noise at x: the generator reads [x | noise] from its own buffer
             _lib.call('tdg_affine_cast_rows', dt, x, rows, 3, self.G.xn.cs, 1.0, 0.0, self.G.xn.ptr(0), K.stream())
         self._target(ybar, crop, y_src)
+        for win in self.G.fed.get('y_bar', ()):                  # mean_provided's fed channel, and the plane the head reads
+            _lib.call('tdg_cgan_bar_fill', dt, K.ptr(ybar), B, win.h * win.w, win.ptr(0), win.cs, K.ptr(self.G.head_u), K.stream())
 
     def _target(self, ybar, crop, y_src=None):
         """The depth half of _inputs: the staged y into the depth target, y_bar and the f32 crop."""
         B, dt, mp2 = self.B, self.sess.dtype, self.version == 2
-        _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage if y_src is None else y_src), B, self.version, self.Dd.x.ptr(0), self.Dd.x.cs,
-                  self.Dd.x.ptr(B) if mp2 else None, K.ptr(ybar), K.ptr(crop),
-                  self.gx.window(3, 1).ptr(0) if mp2 else None, self.gx.cs,
-                  self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs, K.stream())
+        dreal, dcs, dfake, rgb_bar, rgb_cs = self._prep_targets()
+        _lib.call('tdg_cgan_prep', dt, K.ptr(self.y_stage if y_src is None else y_src), B, PREP_VERSION[self.version], dreal, dcs,
+                  dfake, K.ptr(ybar), K.ptr(crop), self.gx.window(3, 1).ptr(0) if mp2 else None, self.gx.cs, rgb_bar, rgb_cs,
+                  K.stream())
 
     def _generate(self, ybar, yhat, g32=None):
         """g (the cropped 1x1 head of the U-Net's last concat) into channel 0 of D's fake depth input, y_hat = g (+ y_bar,
@@ -272,86 +257,6 @@ class CganReplica(engine.Replica):
                       K.ptr(st.grad(name(self.head, 'weights'))), K.ptr(st.grad(name(self.head, 'bias'))),
                       K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
         self.G.backward()
-
-    def _d_forward(self):
-        B, dt = self.B, self.sess.dtype
-        self.Dr.forward(0, B)
-        self.Dd.forward(0, 2 * B)
-        rh, dh = self.Dr.layers[-1].h, self.Dd.layers[-1].h
-        _lib.call('tdg_cgan_join', dt, 0, B, 2 * B, 512, self.Dc.x.ptr(0), self.Dc.x.cs, rh.ptr(0), rh.cs, dh.ptr(0), dh.cs, K.stream())
-        self.Dc.forward(0, 2 * B)
-
-    def _loss(self, mode):
-        last = self.Dc.layers[-1]
-        if self.wgan:
-            _lib.call('tdg_cgan_wgan_loss', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
-                      K.ptr(self.scal), K.stream())
-        else:        # tdg_p2p_xent writes d_real, d_fake, g_fake to scal[0..2] of the pointer, here self.scal[4..6] (_losses)
-            _lib.call('tdg_p2p_xent', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
-                      K.ptr(self.scal, 16), K.stream())
-
-    def _clip(self, store, repack):
-        """--wgan_clip c (opt-in; :181-187 never runs in the reference, SURVEY App. C-3): clamp before the step."""
-        c = float(getattr(self.args, 'wgan_clip', 0.0) or 0.0)
-        if self.wgan and c > 0.0:
-            _lib.call('tdg_clamp', K.ptr(store.params), store.size, -c, c, K.stream())
-            repack()
-
-    # ---- steps ---------------------------------------------------------------------------------------------
-    def d_step(self, batch):
-        self._stage(batch)
-        self.optimizer_step(self.d_store, ('d_grads', self._d_grads), ('d_apply', self._d_apply), 'd_step')
-
-    def _d_grads(self):
-        B, dt = self.B, self.sess.dtype
-        self._clip(self.d_store, self._repack_d)
-        self._inputs(self.ybar, self.crop)
-        self._generate(self.ybar, self.yhat)
-        self._d_forward()
-        self._loss(1)
-        self.Dc.backward(0, 2 * B, want_params=True, want_dx=True)
-        dx = self.Dc.dx
-        _lib.call('tdg_cgan_join', dt, 1, B, 2 * B, 512, dx.ptr(0), dx.cs, self.rgb_g.ptr(0), self.rgb_g.cs, self.depth_g.ptr(0),
-                  self.depth_g.cs, K.stream())
-        self.Dd.backward(0, 2 * B, want_params=True)
-        self.Dr.backward(0, B, want_params=True)
-
-    def _d_apply(self):
-        self.d_opt.step(self._scale)
-        self._repack_d()
-
-    def g_step(self, batch):
-        self._stage(batch)
-        self.optimizer_step(self.g_store, ('g_grads', self._g_grads), ('g_apply', self._g_apply), 'g_step')
-
-    def _g_grads(self):
-        """The G step and the loss fetch of one sess.run (:208): D runs on both halves, the losses are this batch's."""
-        B, dt = self.B, self.sess.dtype
-        self._clip(self.g_store, self.G.repack)
-        self._inputs(self.ybar, self.crop)
-        self._generate(self.ybar, self.yhat)
-        self._d_forward()
-        self._loss(2)
-        self.Dc.backward(B, B, want_params=False, want_dx=True)
-        dx = self.Dc.dx
-        _lib.call('tdg_cgan_join', dt, 1, B, B, 512, dx.ptr(B), dx.cs, None, 0, self.depth_g.ptr(B), self.depth_g.cs, K.stream())
-        self.Dd.backward(B, B, want_params=False, want_dx=True)
-        self._g_backward()
-
-    def _g_apply(self):
-        self.g_opt.step(self._scale)
-        self.G.repack()
-
-    def _losses(self):
-        s = self.sess.report_scalars(self.scal, mean=getattr(self.args, 'mean_loss', False)).cpu().tolist()
-        r = self.sess.world_size - 1
-        if self.wgan:                    # :396-403: the real mean is named 'd_fake' again -> 'd_fake_1'
-            items = [('loss/generator/g_fake', s[0]), ('loss/discriminator/d_fake', s[1]), ('loss/discriminator/d_fake_1', s[2]),
-                     ('loss/discriminator/d_total', s[3])]
-        else:                            # :398-407 (scal[4..6] = d_real, d_fake, g_fake of tdg_p2p_xent)
-            items = [('loss/generator/g_fake', s[6]), ('loss/discriminator/d_fake', s[5]), ('loss/discriminator/d_real', s[4]),
-                     ('loss/discriminator/d_total', s[4] + s[5])]
-        return collection_to_dict([('tower_%d/%s:0' % (r, n), v) for n, v in items])
 
     # ---- evaluation ----------------------------------------------------------------------------------------
     def metrics(self):
@@ -524,6 +429,169 @@ class CganReplica(engine.Replica):
         self._generate(self.inf_ybar, self.inf_yhat)
         _lib.call('tdg_cgan_full_store', K.ptr(self.inf_yhat), K.ptr(self.inf_ybar) if self.version != 0 else None, self.B, fb.slots,
                   K.ptr(fb.chunk), K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), K.stream())
+
+
+class CganReplica(GeneratorReplica):
+    """What the thesis' depth cGAN plugins share (paper_cgan here, paper_sampler / paper_noise in models/sampler/):
+    GeneratorReplica with the critic on top -- D's builder and networks, the join, the losses, the D and G steps.  g lands in
+    D's fake depth input and dL/dg is read from that input's gradient."""
+
+    @staticmethod
+    def discriminator(x, y, args, reuse=False):
+        """d_baseline (:312-338) / d_mean_provided2 (:362-388, x and y already carry their y_bar channel).
+        Returns the logits [B,1,1,1] and the two path outputs."""
+        with arg_scope([conv2d], reuse=reuse, activation=_lrelu(0.2), init='xavier', padding='VALID', filter_size=5, stride=2):
+            with variable_scope('rgb_path'):
+                h1 = conv2d(x, x.shape[-1], 64, name='hx1')     # 31x31x64
+                h1 = conv2d(h1, 64, 128, name='hx2')            # 14x14x128
+                h1 = conv2d(h1, 128, 256, name='hx3')           # 5x5x256
+                h1 = conv2d(h1, 256, 512, name='hx4')           # 1x1x512
+            with variable_scope('depth_path'):
+                h2 = conv2d(y, y.shape[-1], 128, name='hy1')    # 13x13x128 (the reference's "14x14" comment at :326 is off)
+                h2 = conv2d(h2, 128, 256, name='hy2')           # 5x5x256
+                h2 = conv2d(h2, 256, 512, name='hy3')           # 1x1x512
+            with variable_scope('combined_path'):
+                h = concat([h1, h2])                            # 1x1x1024
+                h = conv2d(h, 1024, 1024, stride=1, filter_size=1, padding='SAME', name='h1')
+                h = conv2d(h, 1024, 512, stride=1, filter_size=1, padding='SAME', name='h2')
+                h = conv2d(h, 512, 1, stride=1, filter_size=1, padding='SAME', name='h3', activation=None)
+        return h, h1, h2
+
+    @classmethod
+    def record_critic(cls, xs, args, mp2):
+        rx = concat([xs, placeholder((None, SRC, SRC, 1), 'y_bar')]) if mp2 else xs
+        dy = placeholder((None, CROP, CROP, 2 if mp2 else 1), 'y')
+        with variable_scope('discriminator'):
+            cls.discriminator(rx, dy, args, reuse=False)             # D(x, y_hat) first, as :123-136
+            cls.discriminator(rx, dy, args, reuse=True)
+
+    # ------------------------------------------------------------------------------ construction
+    S_GFAKE, S_DFAKE, S_DREAL, S_DTOTAL = 0, 1, 2, 3
+
+    def _build_critic(self, nets, args):
+        B, dev, dt, mp2 = self.B, self.sess.device, self.sess.dtype, self.version == 2
+        self.wgan = getattr(args, 'training_version', 'gan') == 'wgan'
+        rgb_net, depth_net, comb_net = (nets['discriminator/' + s] for s in ('rgb_path', 'depth_path', 'combined_path'))
+        self.d_store = engine.ParamStore(dev)
+        # D: combined path over 2B (images [0,B) real, [B,2B) fake), depth path over 2B, rgb path over B
+        self.Dc = engine.SeqNet(comb_net, 2 * B, (1, 1, 1024), dt, dev, self.d_store, need_input_grad=True, ws=self.ws)
+        self.Dr = engine.SeqNet(rgb_net, B, (SRC, SRC, 4 if mp2 else 3), dt, dev, self.d_store, ws=self.ws)
+        self.Dd = engine.SeqNet(depth_net, 2 * B, (CROP, CROP, 2 if mp2 else 1), dt, dev, self.d_store, need_input_grad=True,
+                                ws=self.ws)
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.declare_variables()
+        self.rgb_g = self.Dr.layers[-1].gout                 # dL/d(rgb path output): both halves summed by tdg_cgan_join
+        self.depth_g = self.Dd.layers[-1].gout
+        return self.Dr.x
+
+    def _g_buffers(self):
+        return self.Dd.x.view(self.B, self.B), self.Dd.dx.view(self.B, self.B)      # g lands in D's fake depth input
+
+    def _allocate(self):
+        self.d_store.allocate()
+        self.g_store.allocate()
+
+    def _setup(self, args, gen):
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.init_variables(gen)
+        if self.wgan:                                        # :64-66
+            self.g_opt = engine.RMSProp(self.g_store, args.g_lr, decay=0.9, momentum=0.0, eps=1e-10)
+            self.d_opt = engine.Adam(self.d_store, args.d_lr)
+        else:                                                # :67-69
+            self.g_opt = engine.Adam(self.g_store, args.g_lr, args.g_beta1, args.g_beta2)
+            self.d_opt = engine.Adam(self.d_store, args.d_lr, args.d_beta1, args.d_beta2)
+        self.register('generator', self.g_store, self.g_opt, self.G.repack)
+        self.register('discriminator', self.d_store, self.d_opt, self._repack_d)
+
+    def _repack_d(self):
+        for net in (self.Dr, self.Dd, self.Dc):
+            net.repack()
+
+    def _prep_targets(self):
+        mp2 = self.version == 2
+        return (self.Dd.x.ptr(0), self.Dd.x.cs, self.Dd.x.ptr(self.B) if mp2 else None,
+                self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs)
+
+    # ---- pieces ------------------------------------------------------------------------------------------
+    def _d_forward(self):
+        B, dt = self.B, self.sess.dtype
+        self.Dr.forward(0, B)
+        self.Dd.forward(0, 2 * B)
+        rh, dh = self.Dr.layers[-1].h, self.Dd.layers[-1].h
+        _lib.call('tdg_cgan_join', dt, 0, B, 2 * B, 512, self.Dc.x.ptr(0), self.Dc.x.cs, rh.ptr(0), rh.cs, dh.ptr(0), dh.cs, K.stream())
+        self.Dc.forward(0, 2 * B)
+
+    def _loss(self, mode):
+        last = self.Dc.layers[-1]
+        if self.wgan:
+            _lib.call('tdg_cgan_wgan_loss', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
+                      K.ptr(self.scal), K.stream())
+        else:        # tdg_p2p_xent writes d_real, d_fake, g_fake to scal[0..2] of the pointer, here self.scal[4..6] (_losses)
+            _lib.call('tdg_p2p_xent', self.sess.dtype, last.h.ptr(0), self.B, last.h.cs, mode, last.gout.ptr(0),
+                      K.ptr(self.scal, 16), K.stream())
+
+    def _clip(self, store, repack):
+        """--wgan_clip c (opt-in; :181-187 never runs in the reference, SURVEY App. C-3): clamp before the step."""
+        c = float(getattr(self.args, 'wgan_clip', 0.0) or 0.0)
+        if self.wgan and c > 0.0:
+            _lib.call('tdg_clamp', K.ptr(store.params), store.size, -c, c, K.stream())
+            repack()
+
+    # ---- steps ---------------------------------------------------------------------------------------------
+    def d_step(self, batch):
+        self._stage(batch)
+        self.optimizer_step(self.d_store, ('d_grads', self._d_grads), ('d_apply', self._d_apply), 'd_step')
+
+    def _d_grads(self):
+        B, dt = self.B, self.sess.dtype
+        self._clip(self.d_store, self._repack_d)
+        self._inputs(self.ybar, self.crop)
+        self._generate(self.ybar, self.yhat)
+        self._d_forward()
+        self._loss(1)
+        self.Dc.backward(0, 2 * B, want_params=True, want_dx=True)
+        dx = self.Dc.dx
+        _lib.call('tdg_cgan_join', dt, 1, B, 2 * B, 512, dx.ptr(0), dx.cs, self.rgb_g.ptr(0), self.rgb_g.cs, self.depth_g.ptr(0),
+                  self.depth_g.cs, K.stream())
+        self.Dd.backward(0, 2 * B, want_params=True)
+        self.Dr.backward(0, B, want_params=True)
+
+    def _d_apply(self):
+        self.d_opt.step(self._scale)
+        self._repack_d()
+
+    def g_step(self, batch):
+        self._stage(batch)
+        self.optimizer_step(self.g_store, ('g_grads', self._g_grads), ('g_apply', self._g_apply), 'g_step')
+
+    def _g_grads(self):
+        """The G step and the loss fetch of one sess.run (:208): D runs on both halves, the losses are this batch's."""
+        B, dt = self.B, self.sess.dtype
+        self._clip(self.g_store, self.G.repack)
+        self._inputs(self.ybar, self.crop)
+        self._generate(self.ybar, self.yhat)
+        self._d_forward()
+        self._loss(2)
+        self.Dc.backward(B, B, want_params=False, want_dx=True)
+        dx = self.Dc.dx
+        _lib.call('tdg_cgan_join', dt, 1, B, B, 512, dx.ptr(B), dx.cs, None, 0, self.depth_g.ptr(B), self.depth_g.cs, K.stream())
+        self.Dd.backward(B, B, want_params=False, want_dx=True)
+        self._g_backward()
+
+    def _g_apply(self):
+        self.g_opt.step(self._scale)
+        self.G.repack()
+
+    def _losses(self):
+        s = self.sess.report_scalars(self.scal, mean=getattr(self.args, 'mean_loss', False)).cpu().tolist()
+        r = self.sess.world_size - 1
+        if self.wgan:                    # :396-403: the real mean is named 'd_fake' again -> 'd_fake_1'
+            items = [('loss/generator/g_fake', s[0]), ('loss/discriminator/d_fake', s[1]), ('loss/discriminator/d_fake_1', s[2]),
+                     ('loss/discriminator/d_total', s[3])]
+        else:                            # :398-407 (scal[4..6] = d_real, d_fake, g_fake of tdg_p2p_xent)
+            items = [('loss/generator/g_fake', s[6]), ('loss/discriminator/d_fake', s[5]), ('loss/discriminator/d_real', s[4]),
+                     ('loss/discriminator/d_total', s[4] + s[5])]
+        return collection_to_dict([('tower_%d/%s:0' % (r, n), v) for n, v in items])
 
 
 class paper_cgan(ModelPlugin, CganReplica):

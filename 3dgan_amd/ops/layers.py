@@ -71,6 +71,7 @@ class LayerSpec:
         self.in_shape, self.out_shape = in_shape, out_shape
         self.padding, self.init = padding, init
         self.noise = None                            # (channels, minval, maxval) of a random_uniform concatenated last onto the input
+        self.fed = None                              # (channels, source) of a placeholder concatenated last onto the input: fed, not drawn
 
     def signature(self):
         return (self.kind, self.name, self.in_size, self.out_size, self.k, self.stride, self.use_bn,
@@ -261,6 +262,18 @@ def _noise_part(x):
     return None
 
 
+def _fed_part(x):
+    """(channels, source) when the last channels of `x` -- the last leaf of its (nested) concats -- are a placeholder's: an extra
+    last channel that is FED per pass (hem/models/paper_standalone.py:176-207: y_bar behind e1), not drawn.  It takes part in no
+    Philox draw."""
+    leaf, nested = x, False
+    while getattr(leaf, 'parts', None) and len(leaf.parts) > 1:
+        leaf, nested = leaf.parts[-1], True
+    if nested and leaf.producer is None and leaf.source not in (None, 'concat', 'random_uniform', 'random_normal'):
+        return leaf.shape[-1], leaf.source
+    return None
+
+
 def _same(in_size, k, stride):
     return -(-in_size // stride)
 
@@ -294,7 +307,7 @@ def conv2d(x, input_size, output_size, filter_size=3, stride=1, init='xavier', u
         oh, ow = -(-(h - filter_size + 1) // stride), -(-(w - filter_size + 1) // stride)
     spec = LayerSpec('conv2d', name, input_size, output_size, filter_size, stride, use_batch_norm, activation,
                      (h, w, c), (oh, ow, output_size), padding, init, use_in=use_in)
-    spec.noise = _noise_part(x)
+    spec.noise, spec.fed = _noise_part(x), _fed_part(x)
     current_net().add(spec, reuse)
     return Sym((None, oh, ow, output_size), producer=spec)
 
@@ -348,6 +361,6 @@ def deconv2d(x, input_size, output_size, filter_size=3, stride=2, init='xavier',
                          % (name, padding, filter_size, stride, oh, ow, h, w))
     spec = LayerSpec('deconv2d', name, input_size, output_size, filter_size, stride, use_batch_norm, activation,
                      (h, w, c), (oh, ow, output_size), padding, init, dropout=dropout, use_in=use_in)
-    spec.noise = _noise_part(x)
+    spec.noise, spec.fed = _noise_part(x), _fed_part(x)
     current_net().add(spec, reuse)
     return Sym((None, oh, ow, output_size), producer=spec)

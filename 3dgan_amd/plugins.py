@@ -38,6 +38,19 @@ def sampler_model_plugins():
     return search_for_plugins(os.path.join(_HERE, 'models', 'sampler'), '3dgan_amd.models.sampler', 'ModelPlugin')
 
 
+def standalone_model_plugins():
+    """The thesis' control experiment (hem/models/paper_standalone.py, paper_baseline_standalone.py):
+    `3dgan_amd/models/standalone/`.  Not part of all_model_plugins(), whose result is pinned; get_model() looks here too."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'standalone'), '3dgan_amd.models.standalone', 'ModelPlugin')
+
+
+def every_model_plugin():
+    """all_model_plugins() and the standalone directory: what `--model` accepts."""
+    found = all_model_plugins()
+    found.update(standalone_model_plugins())
+    return found
+
+
 def all_model_plugins():
     """Every `--model` plugin: the three directories."""
     found = model_plugins()
@@ -52,7 +65,7 @@ def data_plugins():
 
 def get_model(name):
     """hem/models/ModelPlugin.py:4-8: the plugin class registered under `name` (KeyError for an unknown name, as there)."""
-    return all_model_plugins()[name]
+    return every_model_plugin()[name]
 
 
 def get_dataset(name):

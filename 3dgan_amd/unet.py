@@ -21,6 +21,11 @@ generator input), 'e1' .. 'e<n>' (behind that encoder output; 'e<n>' is the late
 layer's skip concat); the injection key of a node is 'noise_<node>' unless `noise_keys` names another.  Every concat stays
 zero-copy -- the layouts are in UNet's docstring.  A head of the caller's that reads a noise channel ('d<n>' without `g_out`)
 gets its f32 draw in `head_u`; the concat is not widened for it.
+The extra last channel of a layer is either DRAWN, as above, or FED: a recorded placeholder concatenated last (`spec.fed`;
+paper_standalone `--model_version mean_provided`, hem/models/paper_standalone.py:176-207: y_bar behind e1 and in front of the
+head).  A fed channel has the layout of a drawn one, takes part in no Philox draw and has no injection key; its windows are in
+`fed[source]` and the caller fills them (and `head_u`, the f32 plane of a fed head channel) before forward().  The padding
+channels behind it stay zero.
 Dropout (`spec.dropout` = keep probability, hem/ops/layers.py:207) runs on the decoder layers that record it.
 """
 import torch
@@ -62,17 +67,22 @@ class UNet:
         A = lambda h, w, c: K.Act(B, h, w, c, dtype, device)
         H, W = E[0].in_shape[:2]
         # noise channels each layer reads behind what its producers provide
-        self.noise_ch = {}                         # node -> channels
+        self.noise_ch = {}                         # node -> channels (drawn or fed: the layouts are the same)
+        self.fed_src = {}                          # node -> placeholder source, for the nodes whose extra channel is fed, not drawn
 
         def extra(node, spec, provided, allowed=(0, 1)):
             ch = spec.in_size - provided
             if ch not in allowed:
                 raise ValueError('layer %s expects %d input channels, its producers provide %d' % (spec.name, spec.in_size, provided))
-            if ch and (spec.noise is None or spec.noise[0] != ch):
-                raise ValueError('layer %s reads %d channels more than its producers provide, and they are no recorded '
-                                 'random_uniform draw' % (spec.name, ch))
+            drawn = spec.noise is not None and spec.noise[0] == ch
+            fed = not drawn and getattr(spec, 'fed', None) is not None and spec.fed[0] == ch
+            if ch and not drawn and not fed:
+                raise ValueError('layer %s reads %d channels more than its producers provide, and they are neither a recorded '
+                                 'random_uniform draw nor a placeholder' % (spec.name, ch))
             if ch:
                 self.noise_ch[node] = ch
+            if ch and fed:
+                self.fed_src[node] = spec.fed[1]
             return ch
         extra('x', E[0], x_in.c)
         for k in range(1, n):
@@ -169,8 +179,17 @@ class UNet:
         reader = dict([('x', E[0])] + [('e%d' % k, E[k]) for k in range(1, n)] + [('e%d' % n, Dc[0])] +
                       [('d%d' % i, Dc[i - 1]) for i in range(2, n + 1)])
         self.noise, self.noise_map, self.head_u = {}, {}, None
+        self.fed = {}                              # placeholder source -> its channel windows; the caller fills them per pass
         for node in reader:
             if node not in self.noise_ch:
+                continue
+            if node in self.fed_src:               # no draw, no key: the order and the keys of the drawn nodes are untouched
+                if self.noise_ch[node] != 1:
+                    raise NotImplementedError('a fed channel behind %s is one channel wide' % node)
+                if node in noise_at:
+                    self.fed.setdefault(self.fed_src[node], []).append(noise_at[node])
+                else:                              # the caller's head reads the fed channel as an f32 plane [B, h, w] of its own
+                    self.head_u = torch.zeros(B * self.top.h * self.top.w, dtype=torch.float32, device=device)
                 continue
             key = (noise_keys or {}).get(node, 'noise_' + node)
             _, lo, hi = reader[node].noise

@@ -358,6 +358,22 @@ int tdg_cgan_sample_stats(const float* y, const float* g, const float* pred, con
                           float image_scale, int n, int hw, float unit, float* out, float* mean_img, float* var_img,
                           void* workspace, size_t workspace_bytes, void* stream);
 size_t tdg_cgan_sample_stats_workspace_bytes(int n, int hw);
+/* ---- paper_standalone (hem/models/paper_standalone.py; 3dgan_amd/csrc/tdg_cgan_standalone.hip) ---------------------------
+ * tdg_cgan_rmse_loss: the regression loss of :244-253 and its gradient for one batch.  y, yhat f32 [n,hw] in depth units (10x);
+ *   d = yhat - y, S = sum d^2, N = n hw:  scal[0] = sqrt(S / N) / 10 = sqrt(mean((yhat/10 - y/10)^2)), one scalar, and
+ *   dg[(b hw + p) dg_cs] = d / (10 sqrt(N S)) = d loss / d yhat in the compute dtype -- channel 0 of a buffer of channel
+ *   stride dg_cs, what tdg_cgan_head_bwd / tdg_cgan_head_noise_bwd read as dfake; no other channel is written.
+ *   Differences, squares and sums in f64, combined in a fixed order without atomics: two launches are bit-equal.  Two launches
+ *   of ceil(N / 1024) blocks (at most 1024): block partials, then every block re-sums them and scales its slice.
+ *   DEVIATION: S == 0 gives loss 0 and a zero gradient (TensorFlow: NaN).
+ *   Workspace: tdg_cgan_rmse_loss_workspace_bytes(n, hw) = 8 min(ceil(n hw / 1024), 1024) bytes (0 for n or hw <= 0). */
+int tdg_cgan_rmse_loss(int dtype, const float* y, const float* yhat, int n, int hw, void* dg, int dg_cs, float* scal,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t tdg_cgan_rmse_loss_workspace_bytes(int n, int hw);
+/* tdg_cgan_bar_fill: the fed y_bar channel of g_mean_provided (:176-207).  win[(b hw2 + p) win_cs] = ybar[b] in the compute
+ *   dtype for b < n, p < hw2 -- one channel of an NHWC window of channel stride win_cs -- and, when `plane` is given,
+ *   plane[b hw2 + p] = ybar[b] (f32).  Nothing else is written. */
+int tdg_cgan_bar_fill(int dtype, const float* ybar, int n, int hw2, void* win, int win_cs, float* plane, void* stream);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Full-frame depth inference of a trained `--model paper_cgan` (the thesis driver `paper_fullimage.py`): the 65x65 window
-slides over whole frames at each `--strides` value, the generator's 29x29 outputs are blended into a frame-sized depth map
-(paper_cgan.infer_full, on the HIP kernels of tdg_cgan_full.hip), and each (frame, stride) prints one JSON line with the
+"""Full-frame depth inference of a trained `--model paper_cgan`, `paper_standalone` or `paper_baseline_standalone` (the
+thesis driver `paper_fullimage.py`): the 65x65 window slides over whole frames at each `--strides` value, the generator's
+29x29 outputs are blended into a frame-sized depth map (infer_full of the model's GeneratorReplica, on the HIP kernels of
+tdg_cgan_full.hip), and each (frame, stride) prints one JSON line with the
 full-frame RMSE.  Unless `--no_images`, the depth, variance and montage images go to `<dir>/images/`, and the montages of
 every frame at one stride are stacked into `full_montage_<s>.png` (:300-315).
 
@@ -65,6 +66,9 @@ def config_tokens(path):
     return out
 
 
+MODELS = ('paper_cgan', 'paper_standalone', 'paper_baseline_standalone')      # the plugins with infer_full() and evaluate()
+
+
 def parse_args(argv=None, own=None, prog='paper_fullimage'):
     """train.py's arguments (3dgan_amd/arguments.parse_args) plus --strides / --split / --frames / --offset / --no_images.
     `@file` arguments are expanded here, so that an options.config written by train.py parses.  `own`: another driver's
@@ -77,8 +81,11 @@ def parse_args(argv=None, own=None, prog='paper_fullimage'):
     args = importlib.import_module('3dgan_amd.arguments').parse_args(rest, warn=lambda m: sys.stderr.write(m + '\n'))
     for k, v in vars(own).items():
         setattr(args, k, v)
-    if args.model != 'paper_cgan':
-        raise SystemExit('%s: --model paper_cgan only (got %r)' % (prog, args.model))
+    if args.model in ('paper_sampler', 'paper_noise'):
+        sampler = importlib.import_module('3dgan_amd.models.sampler.paper_sampler').SamplerReplica
+        raise SystemExit('%s: %s' % (prog, sampler._WHY_NOT % ('infer_full / evaluate', args.model)))
+    if args.model not in MODELS:
+        raise SystemExit('%s: --model %s only (got %r)' % (prog, ' | '.join(MODELS), args.model))
     if any(s < 1 for s in getattr(args, 'strides', ())):
         raise SystemExit('paper_fullimage: every --strides value must be >= 1')
     return args
@@ -96,17 +103,17 @@ def latest_checkpoint(d):
 
 
 def build_model(args):
-    """The trained model: paper_cgan with args' batch size, version and precision, restored from the newest checkpoint."""
+    """The trained model: args.model with args' batch size, version and precision, restored from the newest checkpoint."""
     K = importlib.import_module('3dgan_amd.kernels')
     rt = importlib.import_module('3dgan_amd.runtime')
     ckpt = importlib.import_module('3dgan_amd.checkpoint')
-    pc = importlib.import_module('3dgan_amd.models.paper.paper_cgan')
+    plugin = importlib.import_module('3dgan_amd.plugins').get_model(args.model)
     last = latest_checkpoint(args.dir)
     if last is None:
-        raise SystemExit('paper_fullimage: no checkpoint-N.npz in %s (train with train.py --model paper_cgan first)' % args.dir)
+        raise SystemExit('paper_fullimage: no checkpoint-N.npz in %s (train with train.py --model %s first)' % (args.dir, args.model))
     args.n_gpus = 1
     sess = rt.Session(dtype=K.BF16 if args.precision == 'bf16' else K.F32, seed=args.seed or 0, rank=0, world_size=1)
-    model = pc.paper_cgan(None, args, sess)
+    model = plugin(None, args, sess)
     ckpt.restore(last, model, sess)
     return model, last
 

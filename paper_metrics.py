@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Dataset evaluation of a trained `--model paper_cgan` (the thesis driver `paper/paper_metrics.py`): for each split, the
+"""Dataset evaluation of a trained `--model paper_cgan`, `paper_standalone` or `paper_baseline_standalone` (the thesis driver `paper/paper_metrics.py`): for each split, the
 Eigen-2014 metrics of the model next to the two trivial predictors it has to beat, the split's mean depth image and g = 0,
 each averaged over the split's batches (paper_cgan.evaluate, on the HIP kernels of tdg_cgan_eval.hip).  Per split: the
 three blocks in the reference's key order, one JSON line, `<dir>/metrics/<split>.json` and, unless `--no_images`,

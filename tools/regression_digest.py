@@ -1,7 +1,9 @@
 """Digests of the variables after one train() of two models that other work must not disturb: paper_cgan
 --model_version mean_adjusted (B = 4, f32, eager) and pix2pix --noise input latent end (B = 1, f32, eager).  Per variable the
 SHA-256 of its float32 bytes and its float64 sum.  `python tools/regression_digest.py OUT.npz` writes them;
-tests/test_gpu_paper_sampler.py compares the tree it runs in against tests/golden/regression_digests.npz."""
+tests/test_gpu_paper_sampler.py compares the tree it runs in against tests/golden/regression_digests.npz.  `--sampler OUT.npz`
+writes the same for the plugins of models/sampler/ (sampler_digests(); tests/golden/sampler_parent_digests.npz, compared by
+tests/test_gpu_paper_standalone.py)."""
 import hashlib
 import importlib
 import os
@@ -42,6 +44,35 @@ def models(device):
     yield 'pix2pix', importlib.import_module('3dgan_amd.models.pix2pix').pix2pix(Pairs(1, 256, 2, 1, device), args, sess)
 
 
+def sampler_models(device):
+    """The plugins of models/sampler/, which run on the skip U-Net executor's noise windows: paper_sampler at e1 and d4 with
+    encoder batch norm and at x without, and paper_noise; each at B = 4, f32, seed 0, eager."""
+    rt = importlib.import_module('3dgan_amd.runtime')
+    hp = dict(g_lr=2e-5, d_lr=1e-5, g_beta1=0.5, d_beta1=0.8, g_beta2=0.99, d_beta2=0.995)
+    for tag, model, node, bn in (('paper_sampler_e1_bn', 'paper_sampler', 'e1', True), ('paper_sampler_d4_bn', 'paper_sampler', 'd4', True),
+                                 ('paper_sampler_x', 'paper_sampler', 'x', False), ('paper_noise', 'paper_noise', 'x', False)):
+        sess = rt.Session(device=device, dtype=0, seed=0, rank=0, world_size=1)
+        if model == 'paper_noise':
+            args = SimpleNamespace(batch_size=4, n_gpus=1, model_version='baseline', seed=0, use_graphs=False, **hp)
+        else:
+            args = SimpleNamespace(batch_size=4, n_gpus=1, noise_layer=node, e_bn='false', e_bn_off=not bn, seed=0, use_graphs=False, **hp)
+        cls = getattr(importlib.import_module('3dgan_amd.models.sampler.' + model), model)
+        yield tag, cls(Pairs(4, 65, 2, 0, device), args, sess)
+
+
+def sampler_digests(device=None):
+    """digests() of sampler_models(): tests/golden/sampler_parent_digests.npz (`python tools/regression_digest.py --sampler OUT.npz`)."""
+    device = device or torch.device('cuda:0')
+    out = {}
+    for name, m in sampler_models(device):
+        m.train(None, None, None)
+        torch.cuda.synchronize()
+        for k, v in sorted(m.variables().items()):
+            a = np.ascontiguousarray(v, dtype=np.float32)
+            out[name + '/' + k] = (hashlib.sha256(a.tobytes()).hexdigest(), float(a.astype(np.float64).sum()))
+    return out
+
+
 def digests(device=None):
     """{'<model>/<variable>': (sha256 hex, float64 sum)} after one train() of each model."""
     device = device or torch.device('cuda:0')
@@ -56,7 +87,10 @@ def digests(device=None):
 
 
 if __name__ == '__main__':
-    d = digests()
+    sampler = sys.argv[1:2] == ['--sampler']
+    if sampler:
+        del sys.argv[1]
+    d = sampler_digests() if sampler else digests()
     names = sorted(d)
     os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
     np.savez(sys.argv[1], names=np.array(names), sha256=np.array([d[k][0] for k in names]), sums=np.array([d[k][1] for k in names]))
