@@ -114,6 +114,8 @@ SIGNATURES = {
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_rmse': (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    'tdg_cgan_full_gather_rep': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'tdg_cgan_full_sample_store': (_i, [_vp, _vp, _vp, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tdg_vae_reparam': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd': (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'tdg_vae_reparam_bwd_kl': (_i, [_i, _vp, _i, _vp, _i, _vp, _i, _f, _i, _i, _vp, _i, _vp]),

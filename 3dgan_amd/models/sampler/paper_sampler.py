@@ -31,7 +31,9 @@ every step rewrites, and leaves the variables, the optimizers and the last fetch
 pass on an image of the caller's and returns the per-pixel mean and variance of the B predictions: an uncertainty map.
 
 Not offered: infer_full and evaluate.  With encoder batch norm a window's output depends on its batch neighbours, so neither a
-sliding window nor a dataset sweep means what it means for paper_cgan.
+sliding window nor a dataset sweep means what it means for paper_cgan.  `sample_full(image, depth)` is the whole-frame entry
+point: every window runs as the sampler set runs image 0 -- a batch of copies of that one window, one draw per copy -- and the
+per-pixel mean and variance over the draws are blended into frame canvases (paper_sample_fullimage.py drives it).
 """
 import torch
 
@@ -41,7 +43,7 @@ from ...ops.layers import conv2d, deconv2d, concat, arg_scope, variable_scope, r
 from ...ops.activations import _lrelu, relu
 from ...util import collection_to_dict
 from ..ModelPlugin import ModelPlugin
-from ..paper.paper_cgan import CganReplica, METRIC_KEYS, SRC, CROP
+from ..paper.paper_cgan import CganReplica, METRIC_KEYS, SRC, CROP, FULL_OFFSET, FULL_RMSE_BLOCKS, _FullBuffers, patch_grid
 
 NODES = ['x', 'e1', 'e2', 'e3', 'e4', 'e4-512', 'd2', 'd3', 'd4']
 STAT_KEYS = ('per_image_rmse/mean', 'per_image_rmse/min', 'g_moments/mean', 'g_moments/var', 'y_hat_moments/mean',
@@ -127,6 +129,7 @@ class SamplerReplica(CganReplica):
         self.samp_eigen = f32(8)
         self.stat_out = {k: f32(6) for k in ('y_hat', 'y_0', 'y_mean', 'y_sampler')}
         self.stat_ws = torch.zeros(_lib.load().tdg_cgan_sample_stats_workspace_bytes(B, CROP * CROP), dtype=torch.uint8, device=dev)
+        self._full_sample = {}                                   # sample_full's frame buffers by (H, W, stride, draws)
 
     # ---- steps -------------------------------------------------------------------------------------------
     def _generate(self, ybar, yhat, g32=None):
@@ -221,6 +224,91 @@ class SamplerReplica(CganReplica):
             out['metrics'] = dict(zip(METRIC_KEYS + STAT_KEYS, self.samp_eigen.cpu().tolist() + self.stat_out['y_sampler'].cpu().tolist()))
         return out
 
+    # ---- whole-frame sampling --------------------------------------------------------------------------------
+    def sample_full(self, image, depth=None, stride=10, offset=FULL_OFFSET, draws=None, windows=False):
+        """Per-pixel mean and variance of the predictions over a whole frame: the 65x65 window slid at `stride` as infer_full
+        of paper_cgan slides it, each window run through the sampler pass -- a batch of copies of that ONE window, one noise
+        draw per copy (:88-101), the one batching of a sliding window that means the same with and without batch norm: a
+        window's result depends on nothing but the window and the draws.
+
+        image f32 [H,W,3], depth f32 [H,W] or [H,W,1] in [0, 1] or None (y_bar is then 0 and the predictions are g).  `draws`
+        (default batch_size) must divide batch_size; with encoder batch norm it must equal batch_size (the batch statistics
+        must be those of one window), without it batch_size / draws windows share a pass.  Per pass one graph-replayed body:
+        tdg_cgan_full_gather_rep into samp_x / samp_y, the sampler pass, tdg_cgan_full_sample_store (the draws' f64 mean and
+        variance per pixel).  Then the reference's blend recurrence, at the reference's +18 offset, on all three canvases.
+
+        The variance canvas is that recurrence applied to the per-window variances -- a blend of variance maps, each over
+        the draws of one window -- NOT a pooled variance of every prediction that covers a pixel.
+
+        Returns a FullSample.  Like sample() it uses the sampler pass's buffers and leaves the variables, the optimizers,
+        the last fetch's results and what metrics() reports for metrics_y_hat / metrics_y_0 alone."""
+        B = self.B
+        draws = B if draws is None else int(draws)
+        if draws < 1 or B % draws:
+            raise ValueError('sample_full: draws %d must divide the batch size %d' % (draws, B))
+        if draws != B and self.encoder_batch_norm(self.args):
+            raise ValueError('sample_full: with batch norm in the encoder a pass must hold ONE window, draws = batch_size = %d (got %d)'
+                             % (B, draws))
+        with_depth = depth is not None
+        image = torch.as_tensor(image)
+        image, depth = self._frame(image, depth if with_depth else torch.zeros(tuple(image.shape[:2])))
+        H, W = int(image.shape[0]), int(image.shape[1])
+        grid = patch_grid(H, W, stride)
+        if grid.patches == 0:
+            raise ValueError('sample_full: no %dx%d window fits a %dx%d frame at stride %d' % (SRC, SRC, H, W, stride))
+        if not 0 <= offset <= SRC - CROP:
+            raise ValueError('sample_full: offset %d outside [0, %d]' % (offset, SRC - CROP))
+        fb = self._full_sample_buffers(H, W, stride, draws, grid)
+        fb.image.copy_(image)
+        fb.depth.copy_(depth)
+        fb.chunk.zero_()
+        name = 'sample_full_%d_%d_%d_%d%s' % (H, W, stride, draws, '' if with_depth else '_g')
+        for _ in range(fb.n_passes):
+            self._run(name, lambda: self._sample_full_pass(fb, H, W, stride, draws, with_depth))
+        P = grid.patches
+        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), fb.slots, H, W, stride, offset,
+                  K.ptr(fb.yhat), K.ptr(fb.g), K.stream())
+        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_var), K.ptr(fb.zero_ybar), fb.slots, H, W, stride, offset,
+                  K.ptr(fb.var), K.ptr(fb.var_g), K.stream())
+        rmse = err_mean = err_min = None
+        if with_depth:
+            _lib.call('tdg_cgan_full_rmse', K.ptr(fb.depth), K.ptr(fb.yhat), H, W, K.ptr(fb.rmse), K.ptr(fb.rmse_ws),
+                      fb.rmse_ws.numel() * 8, K.stream())
+            err_mean, err_min = fb.store_err[:P].double().mean(dim=0).cpu().tolist()
+            rmse = float(fb.rmse.item())
+        out = FullSample(fb.yhat.clone(), fb.g.clone(), fb.var.clone(), rmse, err_mean, err_min, P, (grid.cols, grid.rows), draws)
+        if windows:
+            out.window_y_hat, out.window_var, out.window_y_bar = fb.store_yhat[:P].clone(), fb.store_var[:P].clone(), fb.store_ybar[:P].clone()
+        return out
+
+    def _full_sample_buffers(self, H, W, stride, draws, grid):
+        """Frame-sized buffers, allocated once per (H, W, stride, draws): the frame, TWO patch stores of n_passes * (B / draws)
+        slots (mean and variance) with y_bar and the two error columns per slot, the three canvases and the RMSE workspace
+        (fixed addresses: the pass body is graph-captured)."""
+        key = (H, W, stride, draws)
+        if key in self._full_sample:
+            return self._full_sample[key]
+        dev, per_pass = self.sess.device, self.B // draws
+        n_passes = -(-grid.patches // per_pass)
+        slots = n_passes * per_pass
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        fb = self._full_sample[key] = _FullBuffers(
+            n_passes=n_passes, slots=slots, image=f32(H, W, 3), depth=f32(H, W), chunk=torch.zeros(1, dtype=torch.int32, device=dev),
+            store_yhat=f32(slots, CROP, CROP), store_var=f32(slots, CROP, CROP), store_ybar=f32(slots), zero_ybar=f32(slots),
+            store_err=f32(slots, 2), yhat=f32(H, W), g=f32(H, W), var=f32(H, W), var_g=f32(H, W),
+            rmse=torch.zeros(1, dtype=torch.float64, device=dev), rmse_ws=torch.zeros(FULL_RMSE_BLOCKS, dtype=torch.float64, device=dev))
+        return fb
+
+    def _sample_full_pass(self, fb, H, W, stride, draws, with_depth):
+        """One pass: its windows, `draws` copies each, into samp_x / samp_y, the sampler pass, the draws' mean / variance /
+        errors into the stores; advances fb.chunk."""
+        _lib.call('tdg_cgan_full_gather_rep', K.ptr(fb.image), K.ptr(fb.depth) if with_depth else None, H, W, stride, K.ptr(fb.chunk),
+                  self.B, draws, K.ptr(self.samp_x), K.ptr(self.samp_y), K.stream())
+        self._sampler_pass()
+        _lib.call('tdg_cgan_full_sample_store', K.ptr(self.samp_yhat), K.ptr(self.samp_ybar), K.ptr(self.samp_crop) if with_depth else None,
+                  self.B, draws, fb.slots, K.ptr(fb.chunk), K.ptr(fb.store_yhat), K.ptr(fb.store_var), K.ptr(fb.store_ybar),
+                  K.ptr(fb.store_err) if with_depth else None, K.stream())
+
     # ---- not offered -----------------------------------------------------------------------------------------
     _WHY_NOT = ('%s is not offered by %s: with batch norm in the encoder a window\'s output depends on the other images of its '
                 'batch, so the result would depend on how the windows are batched')
@@ -230,6 +318,23 @@ class SamplerReplica(CganReplica):
 
     def evaluate(self, *a, **kw):
         raise NotImplementedError(self._WHY_NOT % ('evaluate', self.name))
+
+
+class FullSample:
+    """sample_full's result: the y_hat, g and var canvases (device f32 [H,W]; y_hat and g in 10x depth like FullFrame's, var in
+    [0, 1] units like sample()'s), rmse (the frame RMSE of the y_hat canvas), err_mean / err_min (the mean over the windows of
+    each window's per_image_rmse/mean and /min over its draws) -- all three None without depth --, patches, grid (cols, rows)
+    and draws.  With windows=True also window_y_hat, window_var [patches,29,29] and window_y_bar [patches]: what was blended."""
+
+    window_y_hat = window_var = window_y_bar = None
+
+    def __init__(self, y_hat, g, var, rmse, err_mean, err_min, patches, grid, draws):
+        self.y_hat, self.g, self.var, self.rmse, self.err_mean, self.err_min = y_hat, g, var, rmse, err_mean, err_min
+        self.patches, self.grid, self.draws = patches, grid, draws
+
+    def __repr__(self):
+        return 'FullSample(%dx%d, patches=%d, grid=%s, draws=%d, rmse=%s)' % (self.y_hat.shape[0], self.y_hat.shape[1], self.patches,
+                                                                              self.grid, self.draws, self.rmse)
 
 
 class paper_sampler(ModelPlugin, SamplerReplica):

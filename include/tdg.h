@@ -405,6 +405,24 @@ int tdg_cgan_full_blend(const float* store_yhat, const float* store_ybar, long l
  * in a workspace of at least 256 doubles, finished in block order by a second launch: deterministic. */
 int tdg_cgan_full_rmse(const float* depth, const float* canvas, int H, int W, double* out, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* ---- whole-frame sampling of paper_sampler / paper_noise (3dgan_amd/csrc/tdg_cgan_full_sample.hip) -----------------------
+ * The grid of tdg_cgan_full_gather with the sampler set's batching (hem/models/paper_sampler.py:88-101): a window's `rep` rows
+ * are copies of that ONE window, one noise draw per copy.
+ * tdg_cgan_full_gather_rep: tdg_cgan_full_gather with every window repeated: row b of x_stage f32 [batch,65,65,3] / y_stage
+ *   f32 [batch,65,65,1] holds patch c = chunk[0] * (batch / rep) + b / rep, zeros where c >= P.  depth is nullable: y_stage
+ *   is then zero.  rep < 1 or batch % rep != 0 is TDG_EINVAL.  With rep == 1 it writes what tdg_cgan_full_gather writes. */
+int tdg_cgan_full_gather_rep(const float* image, const float* depth, int H, int W, int stride, const int* chunk, int batch, int rep,
+                             float* x_stage, float* y_stage, void* stream);
+/* tdg_cgan_full_sample_store: yhat f32 [batch,29,29] as batch / draws groups of `draws` consecutive rows; group k goes to slot
+ *   s = chunk[0] * (batch / draws) + k:  store_yhat[s,p] = the f64 mean over the group's rows of yhat[b,p] as f32 (10x depth, as
+ *   tdg_cgan_full_store writes);  store_var[s,p] = their two-pass f64 population variance / 100 as f32 ([0, 1] units);
+ *   store_ybar[s] = ybar of the group's first row (ybar nullable: 0);  with crop f32 [batch,29,29] (crop and store_err both or
+ *   neither), a_b = mean_p |crop[b,p] - yhat[b,p]| per row and store_err[s,0], [s,1] = the mean and the min of a_b over the
+ *   group / 10 (per_image_rmse/mean and /min of tdg_cgan_sample_stats, per window).  Then chunk[0] += 1 (a second launch).  A
+ *   call whose slots would pass `slots` writes nothing but still advances.  draws < 1 or batch % draws != 0 is TDG_EINVAL.
+ *   Fixed-order f64 reductions (no atomics): two launches are bit-equal. */
+int tdg_cgan_full_sample_store(const float* yhat, const float* ybar, const float* crop, int batch, int draws, long long slots,
+                               int* chunk, float* store_yhat, float* store_var, float* store_ybar, float* store_err, void* stream);
 /* ---- VAE pieces (models/vae.py:66-90,113-129) -------------------------------------------------------
  * heads = [z_mean | z_stddev] rows of 2L (channel stride hs); z = mean + stddev * eps (models/vae.py:128) */
 int tdg_vae_reparam(int dtype, const void* heads, int hs, const void* eps, int es, int rows, int L, void* z, int zs,
