@@ -1157,6 +1157,16 @@ __global__ void __launch_bounds__(256) reduce_final_kernel(const float* __restri
   s = block_sum256(s, sh);
   if (threadIdx.x == 0) acc[blockIdx.x] = (beta != 0.f ? beta * acc[blockIdx.x] : 0.f) + scale * s;
 }
+// out[seg] = sum(x[seg * np ...]) / np, one correctly rounded division: within half an ulp of the exact sum over np.  (scale = 1 / np
+// in the kernel above rounds twice: 1.03 ulp off at np = 255, sum -31.  For a power-of-two np both forms give the same bits.)
+__global__ void __launch_bounds__(256) reduce_mean_kernel(const float* __restrict__ partial, int np, float* __restrict__ out) {
+  __shared__ float sh[4];
+  const float* p = partial + (size_t)blockIdx.x * np;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < np; i += 256) s += p[i];
+  s = block_sum256(s, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = s / (float)np;
+}
 extern "C" int tdg_sumsq(int dtype, const void* x, size_t n, float* acc, float beta, void* workspace,
                          size_t workspace_bytes, void* stream) {
   TDG_CHECK_ARG(x && acc && workspace && n > 0, "tdg_sumsq: bad argument");
@@ -1184,7 +1194,7 @@ extern "C" int tdg_gp_sumsq(int dtype, const void* x, size_t n, float* sumsq, fl
 }
 extern "C" int tdg_mean_segments_f32(const float* x, int nseg, int seglen, float* out, void* stream) {
   TDG_CHECK_ARG(x && out && nseg > 0 && nseg <= 65535 && seglen > 0, "tdg_mean_segments_f32: bad argument");
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(nseg), dim3(256), 0, (hipStream_t)stream, x, seglen, out, 0.f, 1.f / (float)seglen);
+  hipLaunchKernelGGL(reduce_mean_kernel, dim3(nseg), dim3(256), 0, (hipStream_t)stream, x, seglen, out);
   TDG_HIP_LAUNCH_CHECK("mean_segments_f32");
   return TDG_OK;
 }
@@ -1197,7 +1207,7 @@ extern "C" int tdg_sum_f32(const float* x, int n, float* out, float beta, void* 
 }
 extern "C" int tdg_mean_f32(const float* x, int n, float* out, void* stream) {
   TDG_CHECK_ARG(x && out && n > 0, "tdg_mean_f32: bad argument");
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, out, 0.f, 1.f / (float)n);
+  hipLaunchKernelGGL(reduce_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, out);
   TDG_HIP_LAUNCH_CHECK("mean_f32");
   return TDG_OK;
 }
