@@ -3,32 +3,7 @@
 // loss on sigmoid outputs and the Eigen-2014 depth metrics.  All of them are memory-bound; wave64 throughout.
 #include "tdg_cgan_metrics.h"
 
-#define DISPATCH_T(dtype, ...)                  \
-  if ((dtype) == TDG_BF16) {                    \
-    using T = bf16_t;                           \
-    __VA_ARGS__                                 \
-  } else if ((dtype) == TDG_F32) {              \
-    using T = float;                            \
-    __VA_ARGS__                                 \
-  } else {                                      \
-    tdg_set_error("bad dtype %d", (int)(dtype));\
-    return TDG_EINVAL;                          \
-  }
-
 namespace {
-
-constexpr int kSrc = 65, kCrop = 29, kOff = 17;          // paper_cgan.py:93-94: crop_to_bounding_box(y * 10, 17, 17, 29, 29)
-
-inline int grid_for(size_t n) {
-  const size_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // eight consecutive channels as f32 (16-byte loads for bf16, two for f32)
 template <typename T>
@@ -79,10 +54,10 @@ __global__ void __launch_bounds__(256) cgan_prep_kernel(const float* __restrict_
     ci[p] = v;
     s += v;
   }
-  s = wsum(s);
+  s = wave_sum(s);
   if ((t & 63) == 0) sh[t >> 6] = s;
   __syncthreads();
-  const float m = (sh[0] + sh[1] + sh[2] + sh[3]) / (float)(kCrop * kCrop);     // every thread: the same order
+  const float m = block_total(sh) / (float)(kCrop * kCrop);     // every thread: the same order
   if (t == 0) ybar[b] = m;
   const size_t d0 = (size_t)b * kCrop * kCrop * dcs;
   for (int p = t; p < kCrop * kCrop; p += 256) {
@@ -246,12 +221,12 @@ __global__ void __launch_bounds__(256) cgan_wgan_kernel(const T* __restrict__ z,
       seed[(size_t)(rows + i) * cs] = from_f32<T>(mode == 1 ? pf * (1.f - pf) * inv : -pf * (1.f - pf) * inv);
     }
   }
-  sr = wsum(sr);
-  sf = wsum(sf);
+  sr = wave_sum(sr);
+  sf = wave_sum(sf);
   if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = sr; sh[1][threadIdx.x >> 6] = sf; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float mr = (sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3]) * inv, mf = (sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3]) * inv;
+    const float mr = block_total(sh[0]) * inv, mf = block_total(sh[1]) * inv;
     scal[0] = -mf;
     scal[1] = mf;
     scal[2] = mr;

@@ -8,14 +8,11 @@
 //   [set * 9 + k]  k < 8: sum over batches of value k of set `set` (METRIC_KEYS order); k = 8: batches added to that set
 //   [27]           batches added to the moments
 //   [28 + p]       sum over batches of the batch mean of pixel p;  [28 + hw + p]  of its batch variance
-#include <math.h>
-
 #include "tdg_cgan_metrics.h"
 
 namespace {
 
 constexpr int kSets = 3, kSetStride = 9, kMomBatches = kSets * kSetStride, kMomBase = kMomBatches + 1;
-constexpr int kMomSlices = 8;                               // waves of a moments block: each takes every 8th image
 constexpr int kScalars = 12;                                // per set: 8 means, 3 final percentages, batches
 
 // ---- fused batch evaluation: the block partition of cgan_metrics_kernel, up to three sets per element ---------------
@@ -57,37 +54,16 @@ __global__ void eval_batch_finish_kernel(const MetricPartial* __restrict__ part,
   a[8] += 1.0;
 }
 
-// ---- per-pixel batch moments (tf.nn.moments(y, axes=0)): a block owns 64 consecutive pixels, wave w the images
-// b = w, w + 8, ...: every load of a wave is one contiguous run of an image.  Two passes in f64: the batch mean, then the
-// mean of the squared deviations from it; the waves' sums are combined in wave order.
-__global__ void __launch_bounds__(64 * kMomSlices) eval_moments_kernel(const float* __restrict__ y, int n, int hw,
-                                                                       double* __restrict__ acc) {
-  __shared__ double sh[kMomSlices][64];
-  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int p = blockIdx.x * 64 + lane;
+// ---- per-pixel batch moments (tf.nn.moments(y, axes=0)): a block owns 64 consecutive pixels, slice_moments does the rest
+__global__ void __launch_bounds__(64 * kSlices) eval_moments_kernel(const float* __restrict__ y, int n, int hw,
+                                                                    double* __restrict__ acc) {
+  __shared__ double sh[kSlices][64];
+  const int p = blockIdx.x * 64 + (threadIdx.x & 63);
   const bool ok = p < hw;
-  double s = 0.0;
-  if (ok)
-    for (int b = sl; b < n; b += kMomSlices) s += (double)y[(size_t)b * hw + p];
-  sh[sl][lane] = s;
-  __syncthreads();
-  double mean = 0.0;
-  for (int k = 0; k < kMomSlices; ++k) mean += sh[k][lane];         // every wave: the same order
-  mean /= (double)n;
-  __syncthreads();
-  double q = 0.0;
-  if (ok)
-    for (int b = sl; b < n; b += kMomSlices) {
-      const double d = (double)y[(size_t)b * hw + p] - mean;
-      q += d * d;
-    }
-  sh[sl][lane] = q;
-  __syncthreads();
-  if (sl == 0 && ok) {
-    double var = 0.0;
-    for (int k = 0; k < kMomSlices; ++k) var += sh[k][lane];
+  const double mean = slice_moments(y, n, hw, p, ok, sh);
+  if (threadIdx.x < 64 && ok) {
     acc[kMomBase + p] += mean;
-    acc[kMomBase + hw + p] += var / (double)n;
+    acc[kMomBase + hw + p] += slice_total(sh) / (double)n;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) acc[kMomBatches] += 1.0;
 }
@@ -143,7 +119,7 @@ extern "C" int tdg_cgan_eval_batch(const float* y, const float* pred, const floa
 extern "C" int tdg_cgan_eval_moments(const float* y, int n, int hw, double* acc, void* stream) {
   TDG_CHECK_ARG(y && acc && n > 0 && hw > 0, "tdg_cgan_eval_moments: bad argument (n %d, hw %d)", n, hw);
   tdg_timing_start("cgan_eval_moments", 0.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(eval_moments_kernel, dim3(tdg_ceil_div(hw, 64)), dim3(64 * kMomSlices), 0, (hipStream_t)stream, y, n, hw, acc);
+  hipLaunchKernelGGL(eval_moments_kernel, dim3(tdg_ceil_div(hw, 64)), dim3(64 * kSlices), 0, (hipStream_t)stream, y, n, hw, acc);
   tdg_timing_stop((hipStream_t)stream);
   TDG_HIP_LAUNCH_CHECK("cgan_eval_moments");
   return TDG_OK;

@@ -2,7 +2,7 @@
 // and the eight values of one set.  Shared by tdg_cgan_metrics (tdg_cgan.hip) and the fused dataset evaluation
 // (tdg_cgan_eval.hip), so that both give the same bits on the same data.
 #pragma once
-#include "tdg_common.h"
+#include "tdg_cgan_common.h"
 
 namespace {
 
@@ -17,12 +17,6 @@ struct MetricPartial {
 inline int metric_blocks(size_t total) {
   const size_t b = (total + 1023) / 1024;
   return (int)(b < 1 ? 1 : (b > (size_t)kMetricBlocks ? (size_t)kMetricBlocks : b));
-}
-
-__device__ __forceinline__ double metric_wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 // per element (a = y / 10, p = pred / 10): |a-p|/p, (a-p)^2/p, (a-p)^2, d^2, d with d = log(a+1e-8) - log(p+1e-8);
@@ -51,7 +45,7 @@ __device__ __forceinline__ void metric_wave_sums(const double* s, const unsigned
   const int wv = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    const double v = metric_wsum(s[k]);
+    const double v = wave_sum(s[k]);
     if ((threadIdx.x & 63) == 0) shd[k][wv] = v;
   }
 #pragma unroll
@@ -65,8 +59,8 @@ __device__ __forceinline__ void metric_wave_sums(const double* s, const unsigned
 
 __device__ __forceinline__ MetricPartial metric_block_total(double (*shd)[4], unsigned long long (*shh)[4]) {
   MetricPartial m;
-  for (int k = 0; k < 5; ++k) m.s[k] = shd[k][0] + shd[k][1] + shd[k][2] + shd[k][3];
-  for (int k = 0; k < 3; ++k) m.hits[k] = shh[k][0] + shh[k][1] + shh[k][2] + shh[k][3];
+  for (int k = 0; k < 5; ++k) m.s[k] = block_total(shd[k]);
+  for (int k = 0; k < 3; ++k) m.hits[k] = block_total(shh[k]);
   return m;
 }
 

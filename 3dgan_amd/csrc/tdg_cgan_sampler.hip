@@ -3,20 +3,11 @@
 // per-pixel mean / variance images of y_hat (the uncertainty map of sample()).  y_hat is rounded in f32 the way the head stores
 // it; everything after that is f64, the variance two-pass.  No float atomics: per-block partials, finished in block, slice and
 // image order, so two launches are bit-equal.  Memory-bound; wave64 throughout.
-#include <math.h>
-
-#include "tdg_common.h"
+#include "tdg_cgan_common.h"
 
 namespace {
 
-constexpr int kSlices = 8;                                   // waves of a block: each takes every 8th image
 constexpr int kMomCols = 4;                                  // block partials behind the n per-image ones: mean g, var g, mean y_hat, var y_hat
-
-__device__ __forceinline__ double wsum64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // the prediction forms of tdg_cgan_eval_batch: image[p] * scale, or pred[b, p] + offset[b] (either nullable: 0), f32
 __device__ __forceinline__ float prediction(const float* pred, const float* offset, const float* image, float scale, int b, int p,
@@ -26,8 +17,9 @@ __device__ __forceinline__ float prediction(const float* pred, const float* offs
 }
 
 // A block owns 64 consecutive pixels, wave w the images b = w, w + 8, ...: every load of a wave is one contiguous run of an
-// image.  part[blk][b] (b < n) = that image's sum of |y - y_hat| over the block's pixels; part[blk][n + k] = the block's sum
-// over its pixels of the batch mean / variance of g (k = 0, 1) and y_hat (k = 2, 3).
+// image -- the recipe of slice_moments (tdg_cgan_common.h), written out here because the first pass also carries the per-image
+// error sums and g and y_hat share its barriers.  part[blk][b] (b < n) = that image's sum of |y - y_hat| over the block's
+// pixels; part[blk][n + k] = the block's sum over its pixels of the batch mean / variance of g (k = 0, 1) and y_hat (k = 2, 3).
 __global__ void __launch_bounds__(64 * kSlices) sample_stats_kernel(const float* __restrict__ y, const float* __restrict__ g,
                                                                     const float* __restrict__ pred, const float* __restrict__ offset,
                                                                     const float* __restrict__ image, float scale, int n, int hw,
@@ -47,7 +39,7 @@ __global__ void __launch_bounds__(64 * kSlices) sample_stats_kernel(const float*
       if (g) sg += (double)g[(size_t)b * hw + p];
       a = fabs((double)y[(size_t)b * hw + p] - yh);
     }
-    a = wsum64(a);
+    a = wave_sum(a);
     if (lane == 0) pb[b] = a;
   }
   sh[0][sl][lane] = sg;
@@ -80,7 +72,7 @@ __global__ void __launch_bounds__(64 * kSlices) sample_stats_kernel(const float*
     mean_img[p] = (float)(my / unit);
     var_img[p] = (float)(vy / (unit * unit));
   }
-  const double t0 = wsum64(ok ? mg : 0.0), t1 = wsum64(ok ? vg : 0.0), t2 = wsum64(ok ? my : 0.0), t3 = wsum64(ok ? vy : 0.0);
+  const double t0 = wave_sum(ok ? mg : 0.0), t1 = wave_sum(ok ? vg : 0.0), t2 = wave_sum(ok ? my : 0.0), t3 = wave_sum(ok ? vy : 0.0);
   if (lane == 0) {
     pb[n] = t0;
     pb[n + 1] = t1;

@@ -8,21 +8,7 @@
 // loads), the second has EVERY block re-sum the few hundred partials in the same order -- the same S in every block -- and
 // scale and store its own 1024 elements; block 0 writes the scalar.  No serial one-block finish.
 // DEVIATION: S == 0 (yhat == y everywhere) gives loss 0 and an all-zero gradient; TensorFlow's sqrt gradient gives NaN there.
-#include <math.h>
-
-#include "tdg_common.h"
-
-#define DISPATCH_T(dtype, ...)                  \
-  if ((dtype) == TDG_BF16) {                    \
-    using T = bf16_t;                           \
-    __VA_ARGS__                                 \
-  } else if ((dtype) == TDG_F32) {              \
-    using T = float;                            \
-    __VA_ARGS__                                 \
-  } else {                                      \
-    tdg_set_error("bad dtype %d", (int)(dtype));\
-    return TDG_EINVAL;                          \
-  }
+#include "tdg_cgan_common.h"
 
 namespace {
 
@@ -36,12 +22,11 @@ inline int rmse_blocks(long long total) {
 
 // the block's sum, the same value in every thread: wave shuffle, then the four wave sums from LDS in wave order
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum(v);
   __syncthreads();                                           // (sh may still be read from an earlier call)
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  return block_total(sh);
 }
 
 // d[0..3] = yhat - y (f64) of the four elements from i on; elements at or past `total` are 0.  VEC: both pointers are
@@ -140,12 +125,10 @@ extern "C" int tdg_cgan_bar_fill(int dtype, const float* ybar, int n, int hw2, v
   TDG_CHECK_ARG(ybar && win && n > 0 && hw2 > 0 && win_cs > 0 && (dtype == TDG_F32 || dtype == TDG_BF16),
                 "tdg_cgan_bar_fill: bad argument (dtype %d, n %d, hw2 %d, win_cs %d)", dtype, n, hw2, win_cs);
   const long long total = (long long)n * hw2;
-  const long long want = (total + 255) / 256;
-  const int nblk = (int)(want > 2048 ? 2048 : want);
   hipStream_t s = (hipStream_t)stream;
   tdg_timing_start("cgan_bar_fill", 0.0, s);
   DISPATCH_T(dtype, {
-    hipLaunchKernelGGL(bar_fill_kernel<T>, dim3(nblk), dim3(256), 0, s, ybar, total, hw2, static_cast<T*>(win), win_cs, plane);
+    hipLaunchKernelGGL(bar_fill_kernel<T>, dim3(grid_for((size_t)total)), dim3(256), 0, s, ybar, total, hw2, static_cast<T*>(win), win_cs, plane);
   })
   tdg_timing_stop(s);
   TDG_HIP_LAUNCH_CHECK("cgan_bar_fill");

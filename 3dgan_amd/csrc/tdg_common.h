@@ -62,6 +62,19 @@ int tdg_launch(const char* name, int max_lds, double flops, hipStream_t s, L&& l
 #define TDG_NAME(...) \
   [&]() -> const char* { static char n_[64] = ""; if (!n_[0]) snprintf(n_, sizeof(n_), __VA_ARGS__); return n_; }()
 
+// `T` = the element type of a runtime dtype code inside the braces; returns TDG_EINVAL from the enclosing function otherwise
+#define DISPATCH_T(dtype, ...)                  \
+  if ((dtype) == TDG_BF16) {                    \
+    using T = bf16_t;                           \
+    __VA_ARGS__                                 \
+  } else if ((dtype) == TDG_F32) {              \
+    using T = float;                            \
+    __VA_ARGS__                                 \
+  } else {                                      \
+    tdg_set_error("bad dtype %d", (int)(dtype));\
+    return TDG_EINVAL;                          \
+  }
+
 static inline int tdg_dtype_size(int dtype) { return dtype == TDG_BF16 ? 2 : 4; }
 static inline int tdg_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline long long tdg_round_up(long long a, long long b) { return (a + b - 1) / b * b; }

@@ -76,18 +76,6 @@ extern "C" int tdg_timing_end(TdgLaunchRecord* out, int capacity, int* count) {
   return TDG_OK;
 }
 
-#define DISPATCH_T(dtype, ...)                  \
-  if ((dtype) == TDG_BF16) {                    \
-    using T = bf16_t;                           \
-    __VA_ARGS__                                 \
-  } else if ((dtype) == TDG_F32) {              \
-    using T = float;                            \
-    __VA_ARGS__                                 \
-  } else {                                      \
-    tdg_set_error("bad dtype %d", (int)(dtype));\
-    return TDG_EINVAL;                          \
-  }
-
 static inline int ew_blocks(size_t n, int per_block = 1024) {
   size_t b = (n + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));

@@ -162,7 +162,7 @@ class GeneratorReplica(engine.Replica):
         self.counts = {k: torch.zeros(4, dtype=torch.int64, device=dev) for k in ('y_hat', 'y_0')}
         self.metric_out = f32(8)
         self.metric_ws = torch.zeros(_lib.load().tdg_cgan_metrics_workspace_bytes(), dtype=torch.uint8, device=dev)
-        self._full = {}                                      # infer_full's frame buffers by (H, W, stride)
+        self._full = {}                                      # _frame_buffers' cache: (H, W, stride) of infer_full, (H, W, stride, draws) of sample_full
         # dataset evaluation (tdg_cgan_eval.hip): the mean image of metrics_y_mean with its own streaming totals (row 2 of
         # [set, 4]), and evaluate()'s accumulators, totals and results
         lib = _lib.load()
@@ -377,22 +377,8 @@ class GeneratorReplica(engine.Replica):
         (device f32 [H,W]), the frame RMSE, the patch count and the grid (cols, rows)."""
         image, depth = self._frame(image, depth)
         H, W = int(image.shape[0]), int(image.shape[1])
-        grid = patch_grid(H, W, stride)
-        if grid.patches == 0:
-            raise ValueError('infer_full: no %dx%d window fits a %dx%d frame at stride %d' % (SRC, SRC, H, W, stride))
-        if not 0 <= offset <= SRC - CROP:
-            raise ValueError('infer_full: offset %d outside [0, %d]' % (offset, SRC - CROP))
-        fb = self._full_buffers(H, W, stride, grid)
-        fb.image.copy_(image)
-        fb.depth.copy_(depth)
-        fb.chunk.zero_()
-        name = 'full_%d_%d_%d' % (H, W, stride)
-        for _ in range(fb.n_chunks):
-            self._run(name, lambda: self._full_chunk(fb, H, W, stride))
-        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), fb.slots, H, W, stride, offset,
-                  K.ptr(fb.yhat), K.ptr(fb.g), K.stream())
-        _lib.call('tdg_cgan_full_rmse', K.ptr(fb.depth), K.ptr(fb.yhat), H, W, K.ptr(fb.rmse), K.ptr(fb.rmse_ws),
-                  fb.rmse_ws.numel() * 8, K.stream())
+        fb, grid = self._frame_sweep('infer_full', image, depth, stride, offset, (H, W, stride), 'full_%d_%d_%d' % (H, W, stride),
+                                     self.B, self._full_chunk)
         return FullFrame(fb.yhat.clone(), fb.g.clone(), float(fb.rmse.item()), grid.patches, (grid.cols, grid.rows))
 
     def _frame(self, image, depth):
@@ -406,19 +392,49 @@ class GeneratorReplica(engine.Replica):
                              % (tuple(image.shape), tuple(depth.shape)))
         return image, depth
 
-    def _full_buffers(self, H, W, stride, grid):
-        """Frame-sized buffers, allocated once per (H, W, stride): the frame itself, the patch store of n_chunks * B
-        slots, the two canvases and the RMSE workspace (fixed addresses: the chunk body is graph-captured)."""
-        key = (H, W, stride)
+    def _frame_sweep(self, what, image, depth, stride, offset, key, name, per_chunk, body, extras=None, rmse=True):
+        """The whole-frame sweep that infer_full and sample_full share, on a frame _frame() has checked: the grid and the
+        offset check (errors prefixed `what`), the frame into its buffers, `body(fb, H, W, stride)` once per chunk of
+        `per_chunk` windows as the graph `name`, the blend of the y_hat store into the y_hat / g canvases and (`rmse`) the
+        frame RMSE.  Returns (buffers, grid); `key` and `extras` are _frame_buffers'."""
+        H, W = int(image.shape[0]), int(image.shape[1])
+        grid = patch_grid(H, W, stride)
+        if grid.patches == 0:
+            raise ValueError('%s: no %dx%d window fits a %dx%d frame at stride %d' % (what, SRC, SRC, H, W, stride))
+        if not 0 <= offset <= SRC - CROP:
+            raise ValueError('%s: offset %d outside [0, %d]' % (what, offset, SRC - CROP))
+        fb = self._frame_buffers(key, H, W, grid, per_chunk, extras)
+        fb.image.copy_(image)
+        fb.depth.copy_(depth)
+        fb.chunk.zero_()
+        for _ in range(fb.n_chunks):
+            self._run(name, lambda: body(fb, H, W, stride))
+        self._blend(fb, fb.store_yhat, fb.store_ybar, H, W, stride, offset, fb.yhat, fb.g)
+        if rmse:
+            _lib.call('tdg_cgan_full_rmse', K.ptr(fb.depth), K.ptr(fb.yhat), H, W, K.ptr(fb.rmse), K.ptr(fb.rmse_ws),
+                      fb.rmse_ws.numel() * 8, K.stream())
+        return fb, grid
+
+    @staticmethod
+    def _blend(fb, store, store_bar, H, W, stride, offset, canvas, canvas_g):
+        _lib.call('tdg_cgan_full_blend', K.ptr(store), K.ptr(store_bar), fb.slots, H, W, stride, offset, K.ptr(canvas), K.ptr(canvas_g),
+                  K.stream())
+
+    def _frame_buffers(self, key, H, W, grid, per_chunk, extras=None):
+        """Frame-sized buffers, allocated once per `key`: the frame itself, the patch store of n_chunks * per_chunk slots, the
+        two canvases and the RMSE workspace (fixed addresses: the chunk body is graph-captured), plus the caller's
+        `extras(slots, f32)`: a dict of further fields."""
         if key in self._full:
             return self._full[key]
-        dev, B = self.sess.device, self.B
-        n_chunks = -(-grid.patches // B)
+        dev = self.sess.device
+        n_chunks = -(-grid.patches // per_chunk)
+        slots = n_chunks * per_chunk
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         fb = self._full[key] = _FullBuffers(
-            n_chunks=n_chunks, slots=n_chunks * B, image=f32(H, W, 3), depth=f32(H, W), chunk=torch.zeros(1, dtype=torch.int32, device=dev),
-            store_yhat=f32(n_chunks * B, CROP, CROP), store_ybar=f32(n_chunks * B), yhat=f32(H, W), g=f32(H, W),
-            rmse=torch.zeros(1, dtype=torch.float64, device=dev), rmse_ws=torch.zeros(FULL_RMSE_BLOCKS, dtype=torch.float64, device=dev))
+            n_chunks=n_chunks, slots=slots, image=f32(H, W, 3), depth=f32(H, W), chunk=torch.zeros(1, dtype=torch.int32, device=dev),
+            store_yhat=f32(slots, CROP, CROP), store_ybar=f32(slots), yhat=f32(H, W), g=f32(H, W),
+            rmse=torch.zeros(1, dtype=torch.float64, device=dev), rmse_ws=torch.zeros(FULL_RMSE_BLOCKS, dtype=torch.float64, device=dev),
+            **(extras(slots, f32) if extras else {}))
         return fb
 
     def _full_chunk(self, fb, H, W, stride):

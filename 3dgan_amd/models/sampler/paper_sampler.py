@@ -43,7 +43,7 @@ from ...ops.layers import conv2d, deconv2d, concat, arg_scope, variable_scope, r
 from ...ops.activations import _lrelu, relu
 from ...util import collection_to_dict
 from ..ModelPlugin import ModelPlugin
-from ..paper.paper_cgan import CganReplica, METRIC_KEYS, SRC, CROP, FULL_OFFSET, FULL_RMSE_BLOCKS, _FullBuffers, patch_grid
+from ..paper.paper_cgan import CganReplica, METRIC_KEYS, SRC, CROP, FULL_OFFSET, FULL_RMSE_BLOCKS, _FullBuffers, patch_grid  # noqa: F401
 
 NODES = ['x', 'e1', 'e2', 'e3', 'e4', 'e4-512', 'd2', 'd3', 'd4']
 STAT_KEYS = ('per_image_rmse/mean', 'per_image_rmse/min', 'g_moments/mean', 'g_moments/var', 'y_hat_moments/mean',
@@ -129,7 +129,7 @@ class SamplerReplica(CganReplica):
         self.samp_eigen = f32(8)
         self.stat_out = {k: f32(6) for k in ('y_hat', 'y_0', 'y_mean', 'y_sampler')}
         self.stat_ws = torch.zeros(_lib.load().tdg_cgan_sample_stats_workspace_bytes(B, CROP * CROP), dtype=torch.uint8, device=dev)
-        self._full_sample = {}                                   # sample_full's frame buffers by (H, W, stride, draws)
+        self._full_sample = self._full                           # sample_full's frame buffers by (H, W, stride, draws): the one cache
 
     # ---- steps -------------------------------------------------------------------------------------------
     def _generate(self, ybar, yhat, g32=None):
@@ -253,51 +253,24 @@ class SamplerReplica(CganReplica):
         image = torch.as_tensor(image)
         image, depth = self._frame(image, depth if with_depth else torch.zeros(tuple(image.shape[:2])))
         H, W = int(image.shape[0]), int(image.shape[1])
-        grid = patch_grid(H, W, stride)
-        if grid.patches == 0:
-            raise ValueError('sample_full: no %dx%d window fits a %dx%d frame at stride %d' % (SRC, SRC, H, W, stride))
-        if not 0 <= offset <= SRC - CROP:
-            raise ValueError('sample_full: offset %d outside [0, %d]' % (offset, SRC - CROP))
-        fb = self._full_sample_buffers(H, W, stride, draws, grid)
-        fb.image.copy_(image)
-        fb.depth.copy_(depth)
-        fb.chunk.zero_()
-        name = 'sample_full_%d_%d_%d_%d%s' % (H, W, stride, draws, '' if with_depth else '_g')
-        for _ in range(fb.n_passes):
-            self._run(name, lambda: self._sample_full_pass(fb, H, W, stride, draws, with_depth))
+        per_pass = B // draws
+        # beside the common buffers: the variance store with its all-zero y_bar, the two error columns per slot, the variance canvases
+        extras = lambda slots, f32: dict(n_passes=slots // per_pass, store_var=f32(slots, CROP, CROP), zero_ybar=f32(slots),
+                                         store_err=f32(slots, 2), var=f32(H, W), var_g=f32(H, W))
+        fb, grid = self._frame_sweep(
+            'sample_full', image, depth, stride, offset, (H, W, stride, draws),
+            'sample_full_%d_%d_%d_%d%s' % (H, W, stride, draws, '' if with_depth else '_g'), per_pass,
+            lambda fb, H, W, stride: self._sample_full_pass(fb, H, W, stride, draws, with_depth), extras, rmse=with_depth)
+        self._blend(fb, fb.store_var, fb.zero_ybar, H, W, stride, offset, fb.var, fb.var_g)
         P = grid.patches
-        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_yhat), K.ptr(fb.store_ybar), fb.slots, H, W, stride, offset,
-                  K.ptr(fb.yhat), K.ptr(fb.g), K.stream())
-        _lib.call('tdg_cgan_full_blend', K.ptr(fb.store_var), K.ptr(fb.zero_ybar), fb.slots, H, W, stride, offset,
-                  K.ptr(fb.var), K.ptr(fb.var_g), K.stream())
         rmse = err_mean = err_min = None
         if with_depth:
-            _lib.call('tdg_cgan_full_rmse', K.ptr(fb.depth), K.ptr(fb.yhat), H, W, K.ptr(fb.rmse), K.ptr(fb.rmse_ws),
-                      fb.rmse_ws.numel() * 8, K.stream())
             err_mean, err_min = fb.store_err[:P].double().mean(dim=0).cpu().tolist()
             rmse = float(fb.rmse.item())
         out = FullSample(fb.yhat.clone(), fb.g.clone(), fb.var.clone(), rmse, err_mean, err_min, P, (grid.cols, grid.rows), draws)
         if windows:
             out.window_y_hat, out.window_var, out.window_y_bar = fb.store_yhat[:P].clone(), fb.store_var[:P].clone(), fb.store_ybar[:P].clone()
         return out
-
-    def _full_sample_buffers(self, H, W, stride, draws, grid):
-        """Frame-sized buffers, allocated once per (H, W, stride, draws): the frame, TWO patch stores of n_passes * (B / draws)
-        slots (mean and variance) with y_bar and the two error columns per slot, the three canvases and the RMSE workspace
-        (fixed addresses: the pass body is graph-captured)."""
-        key = (H, W, stride, draws)
-        if key in self._full_sample:
-            return self._full_sample[key]
-        dev, per_pass = self.sess.device, self.B // draws
-        n_passes = -(-grid.patches // per_pass)
-        slots = n_passes * per_pass
-        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        fb = self._full_sample[key] = _FullBuffers(
-            n_passes=n_passes, slots=slots, image=f32(H, W, 3), depth=f32(H, W), chunk=torch.zeros(1, dtype=torch.int32, device=dev),
-            store_yhat=f32(slots, CROP, CROP), store_var=f32(slots, CROP, CROP), store_ybar=f32(slots), zero_ybar=f32(slots),
-            store_err=f32(slots, 2), yhat=f32(H, W), g=f32(H, W), var=f32(H, W), var_g=f32(H, W),
-            rmse=torch.zeros(1, dtype=torch.float64, device=dev), rmse_ws=torch.zeros(FULL_RMSE_BLOCKS, dtype=torch.float64, device=dev))
-        return fb
 
     def _sample_full_pass(self, fb, H, W, stride, draws, with_depth):
         """One pass: its windows, `draws` copies each, into samp_x / samp_y, the sampler pass, the draws' mean / variance /

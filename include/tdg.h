@@ -405,7 +405,7 @@ int tdg_cgan_full_blend(const float* store_yhat, const float* store_ybar, long l
  * in a workspace of at least 256 doubles, finished in block order by a second launch: deterministic. */
 int tdg_cgan_full_rmse(const float* depth, const float* canvas, int H, int W, double* out, void* workspace, size_t workspace_bytes,
                        void* stream);
-/* ---- whole-frame sampling of paper_sampler / paper_noise (3dgan_amd/csrc/tdg_cgan_full_sample.hip) -----------------------
+/* ---- whole-frame sampling of paper_sampler / paper_noise (3dgan_amd/csrc/tdg_cgan_full.hip) ------------------------------
  * The grid of tdg_cgan_full_gather with the sampler set's batching (hem/models/paper_sampler.py:88-101): a window's `rep` rows
  * are copies of that ONE window, one noise draw per copy.
  * tdg_cgan_full_gather_rep: tdg_cgan_full_gather with every window repeated: row b of x_stage f32 [batch,65,65,3] / y_stage

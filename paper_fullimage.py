@@ -69,10 +69,11 @@ def config_tokens(path):
 MODELS = ('paper_cgan', 'paper_standalone', 'paper_baseline_standalone')      # the plugins with infer_full() and evaluate()
 
 
-def parse_args(argv=None, own=None, prog='paper_fullimage'):
+def parse_args(argv=None, own=None, prog='paper_fullimage', models=MODELS, check=None):
     """train.py's arguments (3dgan_amd/arguments.parse_args) plus --strides / --split / --frames / --offset / --no_images.
     `@file` arguments are expanded here, so that an options.config written by train.py parses.  `own`: another driver's
-    parser of its own flags in place of own_parser() (paper_metrics.py), `prog` its name in the messages."""
+    parser of its own flags in place of own_parser() (paper_metrics.py, paper_sample_fullimage.py), `prog` its name in the
+    messages, `models` the plugins it accepts and `check(args)` its further checks."""
     argv = sys.argv[1:] if argv is None else list(argv)
     expanded = []
     for a in argv:
@@ -81,13 +82,15 @@ def parse_args(argv=None, own=None, prog='paper_fullimage'):
     args = importlib.import_module('3dgan_amd.arguments').parse_args(rest, warn=lambda m: sys.stderr.write(m + '\n'))
     for k, v in vars(own).items():
         setattr(args, k, v)
-    if args.model in ('paper_sampler', 'paper_noise'):
+    if args.model not in models and args.model in ('paper_sampler', 'paper_noise'):
         sampler = importlib.import_module('3dgan_amd.models.sampler.paper_sampler').SamplerReplica
         raise SystemExit('%s: %s' % (prog, sampler._WHY_NOT % ('infer_full / evaluate', args.model)))
-    if args.model not in MODELS:
-        raise SystemExit('%s: --model %s only (got %r)' % (prog, ' | '.join(MODELS), args.model))
+    if args.model not in models:
+        raise SystemExit('%s: --model %s only (got %r)' % (prog, ' | '.join(models), args.model))
     if any(s < 1 for s in getattr(args, 'strides', ())):
-        raise SystemExit('paper_fullimage: every --strides value must be >= 1')
+        raise SystemExit('%s: every --strides value must be >= 1' % prog)
+    if check:
+        check(args)
     return args
 
 
@@ -153,8 +156,9 @@ def jet(v):
 
 
 def frame_images(image, depth, y_hat, g):
-    """(depth, variance, montage) images in [0, 1]: predicted depth y_hat / 10 clipped to [0, 1] in jet colours, the g
-    canvas min-max normalised (grey), and the montage [image | ground truth | prediction | variance] (:165-212)."""
+    """(depth, variance, montage) images in [0, 1]: predicted depth y_hat / 10 clipped to [0, 1] in jet colours, the second
+    canvas -- infer_full's g (:165-212), sample_full's variance -- min-max normalised (grey), and the montage
+    [image | ground truth | prediction | variance]."""
     import numpy as np
     pred = jet(np.clip(y_hat / 10.0, 0.0, 1.0))
     lo, hi = float(g.min()), float(g.max())
@@ -164,8 +168,10 @@ def frame_images(image, depth, y_hat, g):
     return pred, var, montage
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def sweep_frames(args, run, line, montage_name):
+    """The loop of the whole-frame drivers over args.strides and args.frames.  `run(model, image, depth, stride)` returns the
+    frame's result and the canvas shown as its variance image; `line(result)` is what the frame's JSON line holds between
+    `patches` and `ms`; the montages of a stride are stacked into `montage_name % stride` under `<dir>/images/`."""
     import numpy as np
     summaries = importlib.import_module('3dgan_amd.summaries')
     frames = load_frames(args)
@@ -177,20 +183,29 @@ def main(argv=None):
         montages = []
         for i, image, depth in frames:
             t0 = time.perf_counter()
-            r = model.infer_full(image, depth, stride=s, offset=args.offset)
+            r, second = run(model, image, depth, s)
             ms = (time.perf_counter() - t0) * 1e3
-            print(json.dumps({'split': args.split, 'frame': i, 'stride': s, 'patches': r.patches, 'rmse': r.rmse,
-                              'ms': round(ms, 3)}), flush=True)
+            print(json.dumps(dict({'split': args.split, 'frame': i, 'stride': s, 'patches': r.patches}, **line(r), ms=round(ms, 3))),
+                  flush=True)
             if args.no_images:
                 continue
-            pred, var, montage = frame_images(image, depth, r.y_hat.cpu().numpy(), r.g.cpu().numpy())
+            pred, var, montage = frame_images(image, depth, r.y_hat.cpu().numpy(), second.cpu().numpy())
             stem = os.path.join(img_dir, '%s_%d_s%d_' % (args.split, i, s))
             summaries.write_png(stem + 'depth.png', pred)
             summaries.write_png(stem + 'variance.png', var)
             summaries.write_png(stem + 'montage.png', montage)
             montages.append(montage)
         if montages:
-            summaries.write_png(os.path.join(img_dir, 'full_montage_%d.png' % s), np.concatenate(montages, axis=0))
+            summaries.write_png(os.path.join(img_dir, montage_name % s), np.concatenate(montages, axis=0))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+
+    def run(model, image, depth, s):
+        r = model.infer_full(image, depth, stride=s, offset=args.offset)
+        return r, r.g
+    sweep_frames(args, run, lambda r: {'rmse': r.rmse}, 'full_montage_%d.png')
 
 
 if __name__ == '__main__':

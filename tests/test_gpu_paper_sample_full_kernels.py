@@ -1,4 +1,4 @@
-"""The two kernels of whole-frame sampling (tdg_cgan_full_sample.hip) on the GPU: tdg_cgan_full_gather_rep against NumPy slices
+"""The two kernels of whole-frame sampling (tdg_cgan_full.hip) on the GPU: tdg_cgan_full_gather_rep against NumPy slices
 of the frame and against tdg_cgan_full_gather, tdg_cgan_full_sample_store against float64 NumPy and _sampler_ref.sample_stats."""
 import numpy as np
 import pytest

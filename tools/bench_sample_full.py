@@ -2,7 +2,7 @@
 warm-up frames, then the wall time of `--steps` frames between two synchronisations):
   1. paper_sampler --noise_layer x with encoder batch norm, draws = 512, stride 10;
   2. paper_sampler --e_bn_off, draws = 512 and 64, strides 10 and 4.
-Each line also has the share of the frame taken by the two kernels of tdg_cgan_full_sample.hip and their ms per launch (one
+Each line also has the share of the frame taken by the sampling kernels of tdg_cgan_full.hip (the repeating gather, the sample store) and their ms per launch (one
 eager frame with the library's per-launch events), beside the yardstick of the statistics kernel measured IN THE SAME RUN: ms
 per cgan_sample_stats launch of one eager metrics() at the same batch size.  One JSON line per (configuration, draws, stride)."""
 import argparse
