@@ -67,6 +67,33 @@ class SyntheticPairSource:
         return self.x[k], self.y[k]
 
 
+class SyntheticEstimatorSource:
+    """The 6-tuple `--model mean_depth_estimator` reads, as the nyuv2 flags `--random_crop 65 65 --include_location
+    --include_originals 53 70` yield it: (x [B,65,65,3], y [B,65,65,1], x_loc, y_loc [B,65,65,1], x_full [B,53,70,3],
+    y_full [B,53,70,1]).  Every depth frame has a level of its own, U(0.1, 0.9), plus U(-0.02, 0.02) noise, so the per-image
+    means the estimator regresses spread over (0.1, 0.9); the crop's depth shares the frame's level.  The location channels
+    are the ramps of a 65 x 65 frame cut whole."""
+
+    def __init__(self, n_batches, batch_size, device, size=65, full=(53, 70), seed=1234, rank=0):
+        g = torch.Generator(device='cpu').manual_seed(seed + 7919 * rank)
+        n, B, (fh, fw) = n_batches, batch_size, full
+        level = torch.rand(n, B, 1, 1, 1, generator=g) * 0.8 + 0.1
+        noise = lambda h, w: (torch.rand(n, B, h, w, 1, generator=g) - 0.5) * 0.04
+        ramp = torch.arange(size, dtype=torch.float64) / (size - 1)
+        self.x = torch.rand(n, B, size, size, 3, generator=g).to(device)
+        self.y = (level + noise(size, size)).to(device)
+        self.x_loc = ramp.float()[None, None, :, None].expand(B, size, size, 1).contiguous().to(device)
+        self.y_loc = ramp.float()[None, :, None, None].expand(B, size, size, 1).contiguous().to(device)
+        self.x_full = torch.rand(n, B, fh, fw, 3, generator=g).to(device)
+        self.y_full = (level + noise(fh, fw)).to(device)
+        self.i = 0
+
+    def next_batch(self):
+        k = self.i % self.x.shape[0]
+        self.i += 1
+        return self.x[k], self.y[k], self.x_loc, self.y_loc, self.x_full[k], self.y_full[k]
+
+
 class StreamingSource:
     """The reference's host pipeline for a dataset that stays in HOST memory (data.py:54-58, train.py:171-174):
     cache -> repeat() -> shuffle(buffer_size) -> batch(batch_size * n_gpus), each tower taking its rows of the batch

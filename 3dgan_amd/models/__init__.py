@@ -20,7 +20,8 @@ def model_funcs():
     return {'gan': gan, 'wgan': gan, 'iwgan': gan, 'vae': vae, 'cnn': cnn, 'pix2pix': plugin_func('pix2pix'),
             'paper_cgan': plugin_func('paper_cgan'), 'paper_sampler': plugin_func('paper_sampler'),
             'paper_noise': plugin_func('paper_noise'), 'paper_standalone': plugin_func('paper_standalone'),
-            'paper_baseline_standalone': plugin_func('paper_baseline_standalone')}
+            'paper_baseline_standalone': plugin_func('paper_baseline_standalone'),
+            'mean_depth_estimator': plugin_func('mean_depth_estimator')}
 
 
 def get_model(name):

@@ -44,10 +44,17 @@ def standalone_model_plugins():
     return search_for_plugins(os.path.join(_HERE, 'models', 'standalone'), '3dgan_amd.models.standalone', 'ModelPlugin')
 
 
+def estimator_model_plugins():
+    """The scene mean-depth regressor (hem/models/mean_depth_estimator.py): `3dgan_amd/models/estimator/`.  Like the standalone
+    directory it stays out of all_model_plugins(), whose result is pinned."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'estimator'), '3dgan_amd.models.estimator', 'ModelPlugin')
+
+
 def every_model_plugin():
-    """all_model_plugins() and the standalone directory: what `--model` accepts."""
+    """all_model_plugins(), the standalone directory and the estimator directory: what `--model` accepts."""
     found = all_model_plugins()
     found.update(standalone_model_plugins())
+    found.update(estimator_model_plugins())
     return found
 
 

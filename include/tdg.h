@@ -374,6 +374,18 @@ size_t tdg_cgan_rmse_loss_workspace_bytes(int n, int hw);
  *   dtype for b < n, p < hw2 -- one channel of an NHWC window of channel stride win_cs -- and, when `plane` is given,
  *   plane[b hw2 + p] = ybar[b] (f32).  Nothing else is written. */
 int tdg_cgan_bar_fill(int dtype, const float* ybar, int n, int hw2, void* win, int win_cs, float* plane, void* stream);
+/* ---- mean_depth_estimator (hem/models/mean_depth_estimator.py:136-147; 3dgan_amd/csrc/tdg_mde.hip) ---------------------------
+ * tdg_mde_loss: the scene mean-depth loss and its gradient seed for one batch.  y_full f32 [n,hw]; m [n] in the compute dtype,
+ *   element i at m[i m_cs] (the network's sigmoid output).  mean_out[i] = f32(mean_p y_full[i,p]): the f64 sum of the image in a
+ *   fixed order, divided once and rounded once.  scal[0] = f32((1/n) sum_i |mean_i - m_i|), every mean_i kept f64, m_i widened
+ *   from its stored type, the n terms added in image order.  seed[i seed_cs] = sign(m_i - mean_i) * f32(1/n) in the compute
+ *   dtype: dL/dm, the gradient with respect to the sigmoid's OUTPUT (the caller applies the activation's derivative).
+ *   DEVIATION: sign(0) = 0 where the reference's sqrt(square(d)) has the gradient NaN.  No atomics: two launches are bit-equal.
+ *   Two launches: one block per image (at most 4096 blocks), then a one-block finish over the n terms.
+ *   Workspace: tdg_mde_loss_workspace_bytes(n) = 8 n bytes (0 for n <= 0), 8-byte aligned. */
+int tdg_mde_loss(int dtype, const float* y_full, int n, int hw, const void* m, int m_cs, float* mean_out, void* seed, int seed_cs,
+                 float* scal, void* workspace, size_t workspace_bytes, void* stream);
+size_t tdg_mde_loss_workspace_bytes(int n);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */
