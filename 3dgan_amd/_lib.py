@@ -112,6 +112,9 @@ SIGNATURES = {
     'tdg_cgan_bar_fill': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp]),
     'tdg_mde_loss': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'tdg_mde_loss_workspace_bytes': (_sz, [_i]),
+    'tdg_xsamp_prep': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'tdg_xsamp_head_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    'tdg_xsamp_head_bwd': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
 """`--dataset synthetic`: the bench / smoke input of SURVEY.md section 8d (not in the reference, which has no way to run
 without its private data): uint8 U{0..255} / 255 images, or (rgb, depth) pairs for --model pix2pix (256 x 256) and
 --model paper_cgan / paper_sampler / paper_noise / paper_standalone / paper_baseline_standalone (65 x 65), or the 6-tuple of
---model mean_depth_estimator (65 x 65 pair, two location channels, 53 x 70 originals)."""
+--model mean_depth_estimator (65 x 65 pair, two location channels, 53 x 70 originals) and of --model experimental_sampler (the same
+at 64 x 64)."""
 from .DataPlugin import DataPlugin
 from ..data import SyntheticSource, SyntheticPairSource, SyntheticEstimatorSource
 
@@ -26,6 +27,8 @@ class SyntheticDataset(DataPlugin):
             return SyntheticPairSource(4, B, sess.device, 65, 1234, sess.rank), 4 * B * sess.world_size, (65, 65, 3)
         if args.model == 'mean_depth_estimator':
             return SyntheticEstimatorSource(4, B, sess.device, 65, (53, 70), 1234, sess.rank), 4 * B * sess.world_size, (65, 65, 3)
+        if args.model == 'experimental_sampler':
+            return SyntheticEstimatorSource(4, B, sess.device, 64, (53, 70), 1234, sess.rank), 4 * B * sess.world_size, (64, 64, 3)
         shape = (32, 32, 3)
         if getattr(args, 'resize', None):
             shape = (args.resize[1], args.resize[0], 3)

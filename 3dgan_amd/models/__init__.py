@@ -21,7 +21,8 @@ def model_funcs():
             'paper_cgan': plugin_func('paper_cgan'), 'paper_sampler': plugin_func('paper_sampler'),
             'paper_noise': plugin_func('paper_noise'), 'paper_standalone': plugin_func('paper_standalone'),
             'paper_baseline_standalone': plugin_func('paper_baseline_standalone'),
-            'mean_depth_estimator': plugin_func('mean_depth_estimator')}
+            'mean_depth_estimator': plugin_func('mean_depth_estimator'),
+            'experimental_sampler': plugin_func('experimental_sampler')}
 
 
 def get_model(name):

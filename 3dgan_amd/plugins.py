@@ -50,11 +50,24 @@ def estimator_model_plugins():
     return search_for_plugins(os.path.join(_HERE, 'models', 'estimator'), '3dgan_amd.models.estimator', 'ModelPlugin')
 
 
+def experimental_model_plugins():
+    """The depth cGAN fed by the estimator (hem/models/experimental_sampler.py): `3dgan_amd/models/experimental/`.  It stays out
+    of every_model_plugin(), whose result is pinned like all_model_plugins()'s; known_model_plugins() adds it."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'experimental'), '3dgan_amd.models.experimental', 'ModelPlugin')
+
+
 def every_model_plugin():
-    """all_model_plugins(), the standalone directory and the estimator directory: what `--model` accepts."""
+    """all_model_plugins(), the standalone directory and the estimator directory."""
     found = all_model_plugins()
     found.update(standalone_model_plugins())
     found.update(estimator_model_plugins())
+    return found
+
+
+def known_model_plugins():
+    """every_model_plugin() and the experimental directory: what `--model` accepts."""
+    found = every_model_plugin()
+    found.update(experimental_model_plugins())
     return found
 
 
@@ -72,7 +85,7 @@ def data_plugins():
 
 def get_model(name):
     """hem/models/ModelPlugin.py:4-8: the plugin class registered under `name` (KeyError for an unknown name, as there)."""
-    return every_model_plugin()[name]
+    return known_model_plugins()[name]
 
 
 def get_dataset(name):

@@ -386,6 +386,34 @@ int tdg_cgan_bar_fill(int dtype, const float* ybar, int n, int hw2, void* win, i
 int tdg_mde_loss(int dtype, const float* y_full, int n, int hw, const void* m, int m_cs, float* mean_out, void* seed, int seed_cs,
                  float* scal, void* workspace, size_t workspace_bytes, void* stream);
 size_t tdg_mde_loss_workspace_bytes(int n);
+/* ---- experimental_sampler (hem/models/experimental_sampler.py; 3dgan_amd/csrc/tdg_xsamp.hip) ---------------------------------
+ * tdg_xsamp_prep: ONE pass over the staged f32 batch that writes every input tensor of a generator and critic pass (:107-149).
+ *   x f32 [n,S,S,3], x_loc, y_loc f32 [n,S,S,1], m f32 [n] (the estimator's mean depth), y f32 [n,S,S,1] (nullable: no depth
+ *   output may then be given); x_rows, y_rows int32 [n] (nullable: the identity), entries in [0, n) -- an entry outside is clamped
+ *   into it, never dereferenced.  With r = x_rows[b], channels 0..5 of pixel p of output row b are
+ *   [fl(2 x[r,p] - 1) (3) | x_loc[r,p] | y_loc[r,p] | m[r]], rounded to the compute dtype and written to g_in (channel stride
+ *   g_cs >= 7) AND to rgb_in (channel stride rgb_cs >= 6), each nullable.  Channel 6 of g_in (the noise) and every padding channel
+ *   are NOT written.  With q = y_rows[b] the depth target fl(2 y[q, off + i, off + j] - 1), i, j < T, goes to channel 0 of
+ *   depth_real [n,T,T,depth_cs] (compute dtype, nullable) and to target f32 [n,T,T] (nullable).  off + T <= S.
+ *   The row maps express the training pass (both null), the sampler set (both all-zero: row 0 broadcast) and the shuffled set
+ *   (x_rows a permutation, y_rows null). */
+int tdg_xsamp_prep(int dtype, const float* x, const float* x_loc, const float* y_loc, const float* m, const float* y, const int* x_rows,
+                   const int* y_rows, int n, int S, int T, int off, void* g_in, int g_cs, void* rgb_in, int rgb_cs, void* depth_real,
+                   int depth_cs, float* target, void* stream);
+/* tdg_xsamp_head_fwd: the generator head d5 (1x1 conv, cin -> 1, tanh) on the FULL hw x hw plane of the last concat
+ *   [n,hw,hw,cs] (:246-248; the reference's "31x31x1" comment is off, the plane is 32x32): z = w . cat + b, accumulated as
+ *   tdg_cgan_head_fwd accumulates it, g = tanhf(z).  g f32 [n,hw,hw]; fake (channel 0 of D's fake depth input, channel stride
+ *   fake_cs, compute dtype) = g rounded.  cin in {64,128,256,512}. */
+int tdg_xsamp_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, const float* w, const float* b, float* g,
+                       void* fake, int fake_cs, void* stream);
+/* tdg_xsamp_head_bwd: from dL/dg (channel 0 of dfake, [n,hw,hw,fake_cs]) and the f32 g tdg_xsamp_head_fwd stored (NOT its
+ *   rounding to the compute dtype): dz = dL/dg * fl(1 - fl(g g)), then the contract of tdg_cgan_head_bwd at crop == hw:
+ *   dcat[p, c] = dz[p] * w[c] * mask(cat[p, c]) (the first writer of dcat); dw[c] = sum_p dz[p] * cat[p, c], db[0] = sum_p dz[p]
+ *   (f32, overwritten; per-image partials in the workspace of n * (cin + 1) floats, summed in image order: deterministic).
+ *   With g == 0 everywhere the three results are tdg_cgan_head_bwd's bit for bit. */
+int tdg_xsamp_head_bwd(int dtype, const void* dfake, int fake_cs, const float* g, const void* cat, int n, int hw, int cin, int cs,
+                       const float* w, int mask_mode, float leak, void* dcat, float* dw, float* db, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */

@@ -53,13 +53,14 @@ def message(s):
     print('\033[1m\033[92m{}\033[0m'.format(s))
 
 
-def maybe_relaunch(args, argv):
+def maybe_relaunch(args, argv, script=None):
     """One process per GPU: when asked for several GPUs and not yet under a launcher, start
-    torch.distributed.run as a child (before anything touches the GPU) and exit with its code."""
+    torch.distributed.run as a child (before anything touches the GPU) and exit with its code.  `script`: the driver to
+    launch (default: this file)."""
     if args.n_gpus <= 1 or 'RANK' in os.environ:
         return
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.n_gpus),
-           '--master-addr', '127.0.0.1', '--master-port', str(29500 + os.getpid() % 1000), os.path.abspath(__file__)] + argv
+           '--master-addr', '127.0.0.1', '--master-port', str(29500 + os.getpid() % 1000), os.path.abspath(script or __file__)] + argv
     sys.exit(subprocess.call(cmd))
 
 
@@ -72,23 +73,12 @@ def latest_checkpoint(d):
     return best
 
 
-def main(argv=None):
-    argv = sys.argv[1:] if argv is None else argv
-    args = parse_args(argv)
-    maybe_relaunch(args, argv)
-    resolve_defaults(args)
-    if args.n_gpus < 1:
-        raise SystemExit('--n_gpus 0: this build has no CPU path (the reference raises NameError here, SURVEY App. C-8)')
-
-    import numpy as np
-    import torch
-    from tqdm import tqdm
+def init_run(args):
+    """Everything of a run that comes before a model: the seed, the process group, the session, the options dump, the input
+    pipeline.  Returns (sess, chief, world, x, iter_per_epoch)."""
     K = importlib.import_module('3dgan_amd.kernels')
     rt = importlib.import_module('3dgan_amd.runtime')
-    util = importlib.import_module('3dgan_amd.util')
     datasets = importlib.import_module('3dgan_amd.datasets')
-    ckpt = importlib.import_module('3dgan_amd.checkpoint')
-    summaries = importlib.import_module('3dgan_amd.summaries')
 
     if args.seed is None:
         args.seed = int.from_bytes(os.urandom(4), 'little')          # train.py:193-194 (kept an int, App. C-12)
@@ -117,17 +107,14 @@ def main(argv=None):
         iter_per_epoch = int(x_count / (args.batch_size * args.n_gpus))     # train.py:222
     else:
         iter_per_epoch = args.epoch_size
+    return sess, chief, world, x, iter_per_epoch
 
-    if chief:
-        message('Initializing model...')
-    models = importlib.import_module('3dgan_amd.models')
-    model_funcs = models.model_funcs()                                      # train.py:240-244
-    if args.model not in model_funcs:
-        raise SystemExit('unknown --model %r (available: %s)' % (args.model, ', '.join(sorted(model_funcs))))
-    train_func = model_funcs[args.model](x, args, sess)                     # train.py:246
-    replica = train_func.replica
 
-    # resume (tf.train.Supervisor restores the newest checkpoint in --dir, train.py:254-259,273)
+def resume(replica, args, sess, chief):
+    """tf.train.Supervisor restores the newest checkpoint in --dir (train.py:254-259,273); every replica then starts from rank
+    0's variables."""
+    rt = importlib.import_module('3dgan_amd.runtime')
+    ckpt = importlib.import_module('3dgan_amd.checkpoint')
     last = latest_checkpoint(args.dir)
     if last is not None:
         ckpt.restore(last, replica, sess)
@@ -137,13 +124,21 @@ def main(argv=None):
         rt.broadcast_store(store)
     replica.refresh()
 
-    start_time = time.time()
+
+def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epochs, saved=None):
+    """The epoch / iteration loop and the checkpoint cadence of train.py:279-329, from sess.global_epoch up to max_epochs.
+    `saved`: the replica whose state the checkpoints hold (default: `replica`, the one that trains)."""
+    from tqdm import tqdm
+    K = importlib.import_module('3dgan_amd.kernels')
+    util = importlib.import_module('3dgan_amd.util')
+    ckpt = importlib.import_module('3dgan_amd.checkpoint')
+    summaries = importlib.import_module('3dgan_amd.summaries')
+    saved = replica if saved is None else saved
     current_epoch = sess.global_epoch
-    max_epochs = current_epoch + int(args.epochs[1:]) if args.epochs[0] == '+' else int(args.epochs)   # train.py:279-282
     status = None
     if sess.global_step == 0 and chief:
         message('Generating baseline checkpoint...')
-        ckpt.save(os.path.join(args.dir, 'checkpoint-0.npz'), replica, sess)                           # train.py:288-291
+        ckpt.save(os.path.join(args.dir, 'checkpoint-0.npz'), saved, sess)                             # train.py:288-291
     if chief:
         message('Starting training...')
     try:
@@ -167,18 +162,48 @@ def main(argv=None):
                 real, fake = replica.samples(args.examples) if hasattr(replica, 'samples') else (None, None)
                 summaries.write_epoch(os.path.join(args.dir, 'summaries'), sess.global_epoch, status or {}, real, fake,
                                       args.examples)                                                   # models/gan.py:93-107
-                ckpt.save(os.path.join(args.dir, 'checkpoint-{}.npz'.format(sess.global_epoch)), replica, sess)   # :329
+                ckpt.save(os.path.join(args.dir, 'checkpoint-{}.npz'.format(sess.global_epoch)), saved, sess)   # :329
                 ckpt.prune(args.dir, getattr(args, 'max_to_keep', 0))                                   # gen-2 --max_to_keep
     except Exception as e:
         # gen-2's convention (hem/util/training.py:173-175): report and leave with -1, the status repeat.sh restarts on
         # (it resumes from the newest checkpoint in --dir); the library's status text travels in the exception
         print('Caught unexpected exception during training:', type(e).__name__, e, flush=True)
         sys.exit(-1)
+
+
+def finish(world, chief, start_time):
+    import torch
     if chief:
         message('\nTraining complete! Elapsed time: {}s'.format(int(time.time() - start_time)))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    args = parse_args(argv)
+    maybe_relaunch(args, argv)
+    resolve_defaults(args)
+    if args.n_gpus < 1:
+        raise SystemExit('--n_gpus 0: this build has no CPU path (the reference raises NameError here, SURVEY App. C-8)')
+    sess, chief, world, x, iter_per_epoch = init_run(args)
+
+    if chief:
+        message('Initializing model...')
+    models = importlib.import_module('3dgan_amd.models')
+    model_funcs = models.model_funcs()                                      # train.py:240-244
+    if args.model not in model_funcs:
+        raise SystemExit('unknown --model %r (available: %s)' % (args.model, ', '.join(sorted(model_funcs))))
+    train_func = model_funcs[args.model](x, args, sess)                     # train.py:246
+    replica = train_func.replica
+    resume(replica, args, sess, chief)
+
+    start_time = time.time()
+    current_epoch = sess.global_epoch
+    max_epochs = current_epoch + int(args.epochs[1:]) if args.epochs[0] == '+' else int(args.epochs)   # train.py:279-282
+    run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epochs)
+    finish(world, chief, start_time)
 
 
 def write_profile(path, records):
