@@ -1350,7 +1350,8 @@ extern "C" int tdg_vae_reparam_bwd(int dtype, const void* dz, int zs, const void
 }
 extern "C" int tdg_vae_reparam_bwd_kl(int dtype, const void* dz, int zs, const void* eps, int es, const void* heads, int hs_in,
                                       float kl_weight, int rows, int L, void* dheads, int hs, void* stream) {
-  TDG_CHECK_ARG(dz && eps && heads && dheads && rows > 0 && L > 0 && hs >= 2 * L && hs_in >= 2 * L, "tdg_vae_reparam_bwd_kl: bad argument");
+  TDG_CHECK_ARG(dz && eps && heads && dheads && rows > 0 && L > 0 && hs >= 2 * L && hs_in >= 2 * L && es >= L && zs >= L,
+                "tdg_vae_reparam_bwd_kl: bad argument");
   DISPATCH_T(dtype, {
     hipLaunchKernelGGL(vae_reparam_bwd_kernel<T>, dim3(ew_blocks((size_t)rows * L, 256)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const T*>(dz), zs, static_cast<const T*>(eps), es, rows, L, static_cast<T*>(dheads), hs,
