@@ -1009,8 +1009,12 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) igemm_fwd_dma_kernel
 // PT_NPB = 3 buffers: phase p is loaded (4 pieces per wave, over 2 steps) as soon as the last step that reads phase p - 3
 // is over; the host only selects this kernel when every phase is then complete two steps before its first read
 // (plan_fwd_patch).
+// The 128-row tile (32 rows per compute wave: 832 clocks of MFMA a step, 400 fewer than the 192-row tile's) has no such
+// spare time: its loaders' issue (~610 clocks) + landing wait (~820) WAS its step (1 544 clocks).  It runs 12-piece patches
+// (its patch is 10 KB) and a 4-stage ring with the wait one step behind the issue (template parameter NS, below):
+// 1 287 clocks a step, the compute waves no longer waiting (launch_fwd_patch128).
 // ============================================================================================
-#define PT_CK 5                        // chunks per patch pixel
+#define PT_CK 5                       // chunks per patch pixel
 #define PT_PIXB (PT_CK * 16)
 #define PT_NPB 3                       // patch buffers
 #define PT_PIECES 16                   // 1 KiB pieces per patch, 4 per loader wave
@@ -1216,7 +1220,11 @@ __device__ __forceinline__ void patch_half1(f32x4 (&acc)[TM][TN], bf16x8 (&fa0)[
 // images or -- IgClass.nbh * nbw > 1 -- BLOCKS of one image (bh x bw anchors, rows in block-major order) whose patch carries a
 // halo of `halo` lattice pixels on every side (out-of-image halo pixels are out-of-range sources = zeros: every tap of every
 // row reads inside its patch).
-template <int BM, int BN, int ABL, int CK = PT_CK, int PIECES = PT_PIECES>
+// NS: filter ring stages.  3: a loader waits for every piece of a step (vmcnt(0)) before the step's barrier.  4: the LAGGED form of
+// the 128-row tile -- behind barrier M(s) a loader issues the filter rows of step s + 3 and waits only for what it issued behind
+// M(s - 1) (a counted vmcnt: this step's pieces stay in flight across M(s + 1)), so a piece has two steps to land and a patch is
+// visible one step later than in the 3-stage form (plan_fwd_patch simulates either schedule).
+template <int BM, int BN, int ABL, int CK = PT_CK, int PIECES = PT_PIECES, int NS = 3>
 __global__ void __launch_bounds__(512, 2) igemm_fwd_patch_kernel(const IgArgs args) {
   using T = bf16_t;
   constexpr int NTHR = 512, CW = 4, LW = 4;
@@ -1224,7 +1232,8 @@ __global__ void __launch_bounds__(512, 2) igemm_fwd_patch_kernel(const IgArgs ar
   constexpr int WMR = BM / CW, TM = WMR / 16, TN = BN / 16;
   constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;      // filter rows kept per stage (whole 8-row piece pairs)
   constexpr int NIB = BNL / 8, NBJ = (NIB + LW - 1) / LW;
-  constexpr int STAGE = BNL * IG_BKB, NS = 3;
+  constexpr int STAGE = BNL * IG_BKB, LAG = NS - 3;
+  static_assert(NS == 3 || NS == 4, "3-stage ring, or 4 stages with the loaders' wait one step behind their issue");
   static_assert(PIECES % LW == 0, "patch pieces are dealt evenly to the loader waves");
   static_assert(BM % (16 * CW) == 0 && BN % 16 == 0 && BN / 16 >= BM / (16 * CW), "tile config: the K step hands out one A fragment per column tile");
   // LDS map: [zero pixel + dummy landing zones | filter ring | patches | chunk table | bias row].  The zero pixel sits at
@@ -1412,39 +1421,69 @@ __global__ void __launch_bounds__(512, 2) igemm_fwd_patch_kernel(const IgArgs ar
       ph_next(pn);
     }
     b_pieces(1);
+    int left = P - 1;                                    // phases still to load
+    unsigned dl = left > 0 ? ph_delta(pn) : 0u;
+    bool early1 = false;                                 // lagged form: patch 1 rides behind the prologue's ring stages
+    if constexpr (LAG) {
+      b_pieces(2);
+      if (left > 0) {
+        a_pieces(pn, dl, IntC<0>{}, IntC<PPW>{});
+        ph_next(pn);
+        --left;
+        dl = left > 0 ? ph_delta(pn) : 0u;
+        early1 = true;
+      }
+    }
     TDG_STAMP(t0);
     s_mma = t0 - ph0;                                    // (stamps: kernel entry -> prologue pieces issued)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ) : "memory");       // stage 0 and patch 0 have landed; stage 1 stays in flight
+    // stage 0 and patch 0 have landed; stage 1 (lagged form: stages 1, 2 and patch 1) stays in flight
+    if constexpr (!LAG) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ) : "memory");
+    } else if (early1) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBJ + PPW) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBJ) : "memory");
+    }
     __builtin_amdgcn_s_barrier();
     TDG_STAMP(php);
     // Patches 1 and 2 are loaded whole (4 pieces per wave) in steps 0 and 1 -- their buffers are free, and with every
     // workgroup of a round in its prologue at once the first loads come from HBM at ~11 B/clk/CU: the prologue only waits for
-    // what step 0 reads.  From patch PT_NPB on: two pieces per step once the buffer's previous phase has been read.
+    // what step 0 reads.  (Lagged form: patch 1 went out in the prologue, patch 2 goes in step 0.)  From patch PT_NPB on: two pieces per step once the buffer's previous phase has been read.
     Ph pf{0, 0, 0};                                      // the phase whose buffer pn takes over (from patch PT_NPB on)
-    int left = P - 1;                                    // phases still to load
     int ready = P > PT_NPB ? (ph_end_chunk(pf) - 1) / 8 + 1 : (1 << 30);
     if (ready < PT_NPB - 1) ready = PT_NPB - 1;          // (steps 0 .. PT_NPB - 2 carry the whole-patch loads)
-    unsigned dl = left > 0 ? ph_delta(pn) : 0u;
     // ONE barrier per K step, in the middle of the compute waves' step (between its two 32-deep halves): behind barrier M(s)
     // the loaders overwrite ring stage s + 2 (= s - 1: read for the last time before M(s)) and wait for those pieces to land
     // before M(s + 1), behind which the compute waves start reading them.  A loader has a whole step for ~550 clocks of issue
     // and the load latency; the compute waves never wait for a second barrier.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // ring stage 1 (requested in the prologue)
+    // Lagged form (NS = 4): the pieces of step s + 3 ride on step s, and the wait at the end of step s leaves exactly the pieces
+    // issued IN step s outstanding (vmcnt counts in issue order): what was issued behind M(s - 1) -- ring stage s + 2 and the patch
+    // pieces behind it -- has landed before M(s + 1), behind which the compute waves first read it.
+    if constexpr (!LAG) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // ring stage 1 (requested in the prologue)
+    } else if (early1) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ + PPW) : "memory");     // ring stage 1; stage 2 and patch 1 stay in flight
+    } else {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ) : "memory");
+    }
     for (int step = 0; step < nsteps; ++step) {
       TDG_STAMP(t0);
       __builtin_amdgcn_s_barrier();                        // M(step)
       TDG_STAMP(t1);
-      if constexpr (ABL != 4) b_pieces(step + 2);
+      if constexpr (ABL != 4) b_pieces(step + NS - 1);
+      int mine = 0;                                        // patch pieces issued in this step: 0, PPW, PPW0 or PPW - PPW0
       if constexpr (ABL == 4) {
-      } else if (step < PT_NPB - 1) {
+      } else if (step < PT_NPB - 1 - LAG) {
         if (left > 0) {
           a_pieces(pn, dl, IntC<0>{}, IntC<PPW>{});
           ph_next(pn);
           --left;
           dl = left > 0 ? ph_delta(pn) : 0u;
+          mine = PPW;
         }
       } else if (step == ready) {
         a_pieces(pn, dl, IntC<0>{}, IntC<PPW0>{});
+        mine = PPW0;
       } else if (step == ready + 1) {
         a_pieces(pn, dl, IntC<PPW0>{}, IntC<PPW>{});
         ph_next(pn);
@@ -1452,11 +1491,20 @@ __global__ void __launch_bounds__(512, 2) igemm_fwd_patch_kernel(const IgArgs ar
         --left;
         ready = left > 0 ? max((ph_end_chunk(pf) - 1) / 8 + 1, step + 1) : (1 << 30);
         dl = left > 0 ? ph_delta(pn) : 0u;
+        mine = PPW - PPW0;
       }
       TDG_STAMP(t2);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (!LAG) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      } else {
+        if (mine == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ) : "memory");
+        else if (mine == PPW - PPW0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ + PPW - PPW0) : "memory");
+        else if (mine == PPW0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ + PPW0) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBJ + PPW) : "memory");
+      }
       s_sync += t1 - t0; s_issue += t2 - t1;
     }
+    if constexpr (LAG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last steps' zero-fill pieces: the epilogue stages over the ring
     __builtin_amdgcn_s_barrier();                          // F: the compute waves are done with ring and patches
   } else {
     // ================================ compute waves ================================
@@ -1554,7 +1602,7 @@ __global__ void __launch_bounds__(512, 2) igemm_fwd_patch_kernel(const IgArgs ar
 #pragma unroll
       for (int i = 0; i < TM; ++i) a1[i] = a1n[i];
       st = stn;
-      s_sync += t2 - t1;
+      s_sync += t2 - t1; s_mma += t1 - t0;               // (stamps: barrier wait; the first half -- the second is the rest of the loop)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                        // F: every wave has read its last fragments (the epilogue stages over ring and patches)
@@ -3397,8 +3445,9 @@ int launch_fwd_dma(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hi
 // the staged epilogue, row tiles of whole images OR of one bh x bw block of an image's anchor grid (then the classes' GH, GW,
 // fd_ghw, fd_gw are rewritten to the block's and nbh, nbw, halo set -- only when the whole plan holds), a source whose
 // sub-lattices all have the same shape, patches that fit PIECES KiB, tap groups in K order, and a phase schedule in which
-// every patch lands two steps before its first read (the loader's own rule, simulated here).
-template <int BM, int BN = 208, int CK = PT_CK, int PIECES = PT_PIECES, bool FORCE_HALO = false>
+// every patch lands two steps before its first read (the loader's own rule, simulated here).  LAG = 1: the 4-stage ring's
+// schedule, in which the loaders' wait runs one step behind their issue and a two-step patch load is visible one step later.
+template <int BM, int BN = 208, int CK = PT_CK, int PIECES = PT_PIECES, bool FORCE_HALO = false, int LAG = 0>
 bool plan_fwd_patch(IgArgs& a, int mmax) {
   const int enabled = getenv("TDG_PATCH") ? atoi(getenv("TDG_PATCH")) : 1;     // diagnostics: 0 = igemm_fwd_dma_kernel, 2 = also on small grids
   if (!enabled || (int)a.fd_ck.d != CK || a.accumulate || (a.N & 3) || (a.Cso & 3)) return false;
@@ -3447,18 +3496,19 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
       const int off = ((dh - ph) / a.sigma) * g.QW + (dw - pw) / a.sigma;
       if (off < -127 || off > 127) return false;
     }
-    // the loader's schedule: phase p (>= PT_NPB) is issued in steps s_p, s_p + 1 and is visible from step s_p + 3
+    // the loader's schedule: phase p (>= PT_NPB) is issued in steps s_p, s_p + 1 and is visible from step s_p + 3 (+ LAG)
     const int P = a.nslices * ng, slc = c.ntaps * CK;
     auto first_chunk = [&](int p) { return (p / ng) * slc + c.grp[p % ng].t0 * CK; };
     auto end_chunk = [&](int p) { return (p / ng) * slc + (c.grp[p % ng].t0 + c.grp[p % ng].nt) * CK; };
-    // patches 1 .. PT_NPB - 1 go out whole in steps 0 .. PT_NPB - 2 (visible to the reads of step issue + 2)
+    // patches 1 .. PT_NPB - 1 go out whole in steps 0 .. PT_NPB - 2 (visible to the reads of step issue + 2); the lagged form
+    // issues each a step earlier -- patch 1 in the prologue -- and sees it a step later: the same rule
     for (int p = 1; p < PT_NPB && p < P; ++p)
       if (first_chunk(p) / 8 < (p - 1) + 2) return false;
     int prev_issue = PT_NPB - 3;                             // (the first two-step load starts at step PT_NPB - 1 at the earliest)
     for (int p = PT_NPB; p < P; ++p) {
       const int ready = (end_chunk(p - PT_NPB) - 1) / 8 + 1;
       const int issue = ready > prev_issue + 2 ? ready : prev_issue + 2;
-      if (first_chunk(p) / 8 < issue + 3) return false;
+      if (first_chunk(p) / 8 < issue + 3 + LAG) return false;
       prev_issue = issue;
     }
   }
@@ -3476,26 +3526,35 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
   return true;
 }
 
-template <int BM, int BN, int CK = PT_CK, int PIECES = PT_PIECES>
+// LDS of one igemm_fwd_patch_kernel workgroup: zero pixel, NS ring stages, the patch buffers, 64 bytes of chunk table per K step
+// of the longest class, the bias row
+template <int BN, int PIECES, int NS>
+size_t fwd_patch_lds(const IgArgs& a) {
+  int smax = 0;
+  for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
+  constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
+  return PT_ZEROB + NS * (size_t)BNL * IG_BKB + PT_NPB * (size_t)PIECES * 1024 + (size_t)smax * 64 + BNL * sizeof(float);
+}
+
+template <int BM, int BN, int CK = PT_CK, int PIECES = PT_PIECES, int NS = 3>
 int launch_fwd_patch(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
   a.n_begin = 0;
   a.ntiles_n = tdg_ceil_div(a.N, BN);
   a.ntiles_m_max = tdg_ceil_div(mmax, BM);
   grant_col_partial(a, epi);
-  int smax = 0;
-  for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
-  constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
-  const size_t lds = PT_ZEROB + 3 * (size_t)BNL * IG_BKB + PT_NPB * (size_t)PIECES * 1024 + (size_t)smax * 64 + BNL * sizeof(float);
+  const size_t lds = fwd_patch_lds<BN, PIECES, NS>(a);
   if (lds > 160 * 1024) {
     tdg_set_error("igemm_fwd_patch: %zu bytes of LDS", lds);
     return TDG_EUNSUPPORTED;
   }
   const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
-  const char* name = TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d>", BM, BN);
+  // (the 128-row tile's diagnostic / fallback forms name their patch pieces and ring stages; the default form keeps the plain name)
+  const char* name = BM == 128 && BN == 208 && (PIECES != 12 || NS != 4) ? TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d,%d,%d>", BM, BN, PIECES, NS)
+                                                                       : TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d>", BM, BN);
   auto go = [&](auto abl) {
     constexpr int ABL = decltype(abl)::value;
-    return tdg_launch<igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES>>(name, 160 * 1024, flops, s, [&] {
-      hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES>), grid, block, lds, s, a);
+    return tdg_launch<igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>>(name, 160 * 1024, flops, s, [&] {
+      hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>), grid, block, lds, s, a);
     });
   };
 #ifdef TDG_STAMPS
@@ -3509,6 +3568,25 @@ int launch_fwd_patch(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, 
   }
 #endif
   return go(IntC<0>{});
+}
+
+// The 128-row tile of igemm_fwd_patch_kernel.  Its patch is 128 lattice pixels x 80 B = 10 KB whatever the geometry (2 images of
+// an 8 x 8 lattice, 8 of a 4 x 4 one), so it takes 12-piece patch buffers, and the 16 KB they free pay for a fourth ring stage:
+// the lagged loader schedule (igemm_fwd_patch_kernel, NS = 4) where 152 704 + 64 x K steps fit the 160 KB (<= 174 steps),
+// the 3-stage form beyond.  TDG_PATCH128 (diagnostics): 0 = the form this one replaced (16 pieces, 3 stages), 1 = 12 pieces, 3
+// stages.  Every form multiplies the same fragments in the same order: the results are bit-equal.  False: no plan applies, nothing launched.
+inline bool launch_fwd_patch128(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s, int* rc) {
+  const int form = getenv("TDG_PATCH128") ? atoi(getenv("TDG_PATCH128")) : 2;
+  constexpr int P128 = 12;
+  if (form >= 2 && fwd_patch_lds<208, P128, 4>(a) <= 160 * 1024 && plan_fwd_patch<128, 208, PT_CK, P128, false, 1>(a, mmax))
+    *rc = launch_fwd_patch<128, 208, PT_CK, P128, 4>(a, mmax, flops, epi, s);
+  else if (form >= 1 && plan_fwd_patch<128, 208, PT_CK, P128>(a, mmax))
+    *rc = launch_fwd_patch<128, 208, PT_CK, P128>(a, mmax, flops, epi, s);
+  else if (plan_fwd_patch<128>(a, mmax))
+    *rc = launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
+  else
+    return false;
+  return true;
 }
 
 // igemm_fwd_bp_kernel: the block-patch plan (on a copy: the classes are rewritten only when everything holds) plus what the
@@ -3580,12 +3658,20 @@ int launch_fwd(IgArgs& a, bool veca, int bn, double flops, const TdgEpilogue* ep
     if (veca && bn == 208 && dma_mode == 1 && !getenv("TDG_DMA_BM") && !getenv("TDG_DMA_NW")) {
       const long long per = (long long)tdg_ceil_div(a.N, 208) * a.nclasses;
       const double c192 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 192), 256) * 192 / 1.0;
-      const double c128 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 128), 256) * 128 / 0.75;   // in the step: 890 - 915 TF against 1170 - 1370
+      // 0.78: what the rounds model needs at the shapes where the two tiles compete, measured in the step with the lagged
+      // 128-row form.  On whole-round launches that form now runs 1 096 - 1 124 TF against the 192-row tile's 1 158 - 1 183
+      // (0.95; it was 0.75), but 0.95 was built and measured: c3 forward at 2 560 images (5 rounds x 128 rows against 4 x 192)
+      // moved to 128 rows and took 166 instead of 156 us (implied 0.78), the two 1 024-image c2 launches (4 x 128 against
+      // 3 x 192) moved and tied at 259 us (implied 0.89), the step 16.45 - 16.49 against 16.43 - 16.50 ms.  Not kept.  More,
+      // smaller tiles pay the ~13 000 clocks outside the K loop and the filter intake more often than the K step's rate
+      // shows.  With 0.78 no launch of the GAN step changes its row tile.
+      const double c128 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 128), 256) * 128 / 0.78;
       const int pbm = getenv("TDG_PATCH_BM") ? atoi(getenv("TDG_PATCH_BM")) : 0;            // diagnostics: force a row tile
       const bool want128 = pbm ? pbm == 128 : c128 < c192 - 1e-9;
-      if (want128 && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
+      int rc = TDG_OK;
+      if (want128 && launch_fwd_patch128(a, mmax, flops, epi, s, &rc)) return rc;
       if (plan_fwd_patch<192>(a, mmax)) return launch_fwd_patch<192, 208>(a, mmax, flops, epi, s);
-      if (!want128 && !pbm && plan_fwd_patch<128>(a, mmax)) return launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
+      if (!want128 && !pbm && launch_fwd_patch128(a, mmax, flops, epi, s, &rc)) return rc;
     }
   }
   if (veca && bn == 208 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0) {

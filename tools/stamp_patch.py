@@ -1,7 +1,7 @@
 """Diagnostics: phases of igemm_fwd_patch_kernel's workgroups (stamps library): prologue, K loop, epilogue in cycles."""
 import importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ['TDG_LIB_PATH'] = os.path.join(ROOT, '3dgan_amd', 'lib3dgan_hip_stamps.so')
+os.environ.setdefault('TDG_LIB_PATH', os.path.join(ROOT, '3dgan_amd', 'lib3dgan_hip_stamps.so'))   # (or another stamps build)
 sys.path.insert(0, ROOT)
 import torch
 K = importlib.import_module('3dgan_amd.kernels')
@@ -35,6 +35,18 @@ pro = (ph[:, 0, 1] - ph[:, 0, 0])[order]
 print('prologue of the first 256 workgroups %.0f, of the rest %.0f' % (pro[:256].mean(), pro[256:].mean() if pro.numel() > 256 else -1))
 for wv in range(8):
     print('wave %d: barrier wait %.0f per step%s' % (wv, (st[:, wv, 2] / st[:, wv, 3]).mean(), '' if wv < 4 else ', piece issue %.0f per step' % (st[:, wv, 0] / st[:, wv, 3]).mean()))
+# the K step of every wave, split (clocks per step, stamp cost included).  Loaders: barrier wait, piece issue, and the rest of
+# the loop = the wait for their pieces to land.  Compute waves: first half, barrier wait, and the rest = the second half.
+loop_all = ph[:, :, 2] - ph[:, :, 1]
+for wv in range(8):
+    per = (loop_all[:, wv] / st[:, wv, 3]).mean()
+    sync = (st[:, wv, 2] / st[:, wv, 3]).mean()
+    if wv < 4:
+        h0 = (st[:, wv, 1] / st[:, wv, 3]).mean()
+        print('step split, compute wave %d: %.0f = first half %.0f + barrier %.0f + second half %.0f' % (wv, per, h0, sync, per - h0 - sync))
+    else:
+        iss = (st[:, wv, 0] / st[:, wv, 3]).mean()
+        print('step split, loader wave %d: %.0f = issue %.0f + landing wait %.0f + barrier %.0f' % (wv, per, iss, per - iss - sync, sync))
 print('compute wave 0: entry -> tables built %.0f cycles; loader wave 4: entry -> prologue pieces issued %.0f cycles' % (st[:, 0, 0].mean(), st[:, 4, 1].mean()))
 qq = qq[:ph.shape[0]] if qq.shape[0] >= ph.shape[0] else qq
 m = qq[qq[:, 0, 3] > 0]
