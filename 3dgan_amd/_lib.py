@@ -62,6 +62,7 @@ SIGNATURES = {
     'tdg_conv2d_bwd_filter_workspace_bytes': (_sz, [_PD, _i]),
     'tdg_conv2d_bwd_filter': (_i, [_PD, _i, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
     'tdg_conv2d_bwd_filter2': (_i, [_PD, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
+    'tdg_conv2d_dispatch': (_i, [_PD, _i, _i, _PE, _i, C.c_char_p, _sz]),
     'tdg_rowdot': (_i, [_i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'tdg_rowouter': (_i, [_i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     'tdg_col_finalize_sum': (_i, [_vp, _i, _i, _vp, _f, _vp]),

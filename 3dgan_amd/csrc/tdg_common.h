@@ -44,7 +44,7 @@ void tdg_timing_stop(hipStream_t s);
 // One kernel launch of a conv entry point.  K's dynamic-LDS limit is raised to max_lds once per process (K = nullptr: the
 // default limit).  `name` is noted for tdg_last_kernel (note = false: an auxiliary pass, which leaves the GEMM's name in
 // place).  `launch` enqueues the kernel, plus any kernel that finishes its work, inside one tdg_timing_* window; then the
-// launch is checked.  `name` must stay valid: a literal or a TDG_NAME buffer.
+// launch is checked.  `name` must stay valid: a literal, or a name kept by the conv host code (kept_name, tdg_igemm.hip).
 template <auto K = nullptr, class L>
 int tdg_launch(const char* name, int max_lds, double flops, hipStream_t s, L&& launch, bool note = true) {
   if constexpr (!std::is_null_pointer_v<decltype(K)>) {
@@ -58,10 +58,6 @@ int tdg_launch(const char* name, int max_lds, double flops, hipStream_t s, L&& l
   TDG_HIP_LAUNCH_CHECK(name);
   return TDG_OK;
 }
-// a kernel variant's name, formatted once per call site and template instantiation of the enclosing launcher
-#define TDG_NAME(...) \
-  [&]() -> const char* { static char n_[64] = ""; if (!n_[0]) snprintf(n_, sizeof(n_), __VA_ARGS__); return n_; }()
-
 // `T` = the element type of a runtime dtype code inside the braces; returns TDG_EINVAL from the enclosing function otherwise
 #define DISPATCH_T(dtype, ...)                  \
   if ((dtype) == TDG_BF16) {                    \

@@ -1,5 +1,5 @@
-// Implicit-GEMM kernel argument blocks shared by tdg_igemm.hip (device) and tdg_conv.cpp-side
-// planning code (host).  gfx950 only.
+// Implicit-GEMM kernel argument blocks: filled by the host-side plans and choices of tdg_igemm.hip, read by its kernels
+// and by tdg_wgrad_patch.hip.  gfx950 only.
 #pragma once
 #include "tdg_common.h"
 

@@ -17,6 +17,7 @@
 //  * Filter gradient: both operands are transposed on the way out of LDS
 //    (ds_read_b64_tr_b16 for bf16, ds_read_b32 for f32), rows split over blockIdx.z into f32
 //    slabs that a second kernel sums in a fixed order (deterministic, no atomics).
+#include <stdarg.h>
 #include <stdlib.h>
 
 #include "tdg_igemm.h"
@@ -1012,7 +1013,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) igemm_fwd_dma_kernel
 // The 128-row tile (32 rows per compute wave: 832 clocks of MFMA a step, 400 fewer than the 192-row tile's) has no such
 // spare time: its loaders' issue (~610 clocks) + landing wait (~820) WAS its step (1 544 clocks).  It runs 12-piece patches
 // (its patch is 10 KB) and a 4-stage ring with the wait one step behind the issue (template parameter NS, below):
-// 1 287 clocks a step, the compute waves no longer waiting (launch_fwd_patch128).
+// 1 287 clocks a step, the compute waves no longer waiting (choose_fwd_patch128).
 // ============================================================================================
 #define PT_CK 5                       // chunks per patch pixel
 #define PT_PIXB (PT_CK * 16)
@@ -3363,6 +3364,79 @@ inline int pick_bn(int n) {
   return w208 < w128 - 1e-9 ? 208 : 128;
 }
 
+// ---- the diagnostic switches of the conv path: one table, one reader -----------------------------------------------------
+// Every TDG_* environment variable the conv host code consults, as X(field, variable, value when unset, meaning).  None is
+// set in the product path; every default is the measured-best form.  The plans and choices below take the struct: only
+// conv_switches() calls getenv (and stamp_ptr() in the diagnostic library).
+// SW_UNSET: a switch whose presence alone matters, or whose absence differs from every value.
+constexpr int SW_UNSET = -0x7fffffff - 1;
+// Read ONCE, by the first conv call of the process; a later change is not seen.
+#define CONV_SWITCHES_ONCE(X)                                                                                                \
+  X(kslice, "TDG_KSLICE", 1, "0 = plain K order in every packed filter (no 5- / 4-chunk slices)")                            \
+  X(taporder, "TDG_TAPORDER", 1, "0 = row-major taps in the stride-2 forward filter")                                        \
+  X(dma_bm, "TDG_DMA_BM", SW_UNSET, "force the row tile of the 208-column LDS-DMA kernel; set at all: no patch kernels")     \
+  X(ring, "TDG_RING", 3, "2 = 2-stage ring on the 192-row LDS-DMA tile")                                                     \
+  X(col2im, "TDG_COL2IM", 1, "0 = fused-class / per-class backward-data kernels instead of GEMM + col2im")                   \
+  X(c2i_maxcol, "TDG_C2I_MAXCOL", 64, "most (tap, channel) columns GEMM + col2im takes (<= 80)")                             \
+  X(c2i_kb, "TDG_C2I_KB", 0, "LDS budget of bwd_col2im_kernel in KiB (0: 32 for one column tile, else 48)")                  \
+  X(fuse, "TDG_FUSE", 1, "0 = one launch-z per parity class instead of bwd_fused_kernel")                                    \
+  X(thin, "TDG_THIN", 1, "0 = implicit-GEMM kernels for thin inputs, 2 = only thin_fwd_kernel's 208-column form")            \
+  X(convn1, "TDG_CONVN1", 1, "0 = the 128 x 16 MFMA tile for one-output-channel convs")                                      \
+  X(wg256, "TDG_WG256", 1, "0 = 128-column tiles in the LDS-DMA filter gradient")                                            \
+  X(wsplit, "TDG_WSPLIT", 0, "force the LDS-DMA filter gradient's split count")                                              \
+  X(wdma_minkk, "TDG_WDMA_MINKK", 128, "smallest K the LDS-DMA filter gradient takes")
+// Read by EVERY entry-point call: the variant tests set these between launches.  TDG_BLOCKPATCH decides a packed filter's
+// K order as well as the launch, so a value that changes between pack and launch makes the kernel read a filter packed in
+// the other order; it keeps its per-call read.
+#define CONV_SWITCHES_CALL(X)                                                                                                \
+  X(dma, "TDG_DMA", 1, "0 = register-staged forward kernel, 3 / 4 = force the 192 / 256-row LDS-DMA tile")                   \
+  X(dma_nw, "TDG_DMA_NW", SW_UNSET, "44 = wave-specialised 192 / 128-row tiles, 8 = every wave loads; set: no patch kernels")\
+  X(ksplit, "TDG_KSPLIT", 0, "split-K: 1 = never, n > 1 = n splits")                                                         \
+  X(patch, "TDG_PATCH", 1, "igemm_fwd_patch_kernel: 0 = never, 2 = also on small grids")                                     \
+  X(patch_bm, "TDG_PATCH_BM", 0, "force its 192- or 128-row tile")                                                           \
+  X(patch128, "TDG_PATCH128", 2, "its 128-row tile: 0 = 16 pieces, 3 stages; 1 = 12 pieces, 3 stages; 2 = lagged 4 stages")  \
+  X(bp, "TDG_BP", 1, "0 = the 4 + 4 wave-specialised patch kernel instead of igemm_fwd_bp_kernel")                           \
+  X(blockpatch, "TDG_BLOCKPATCH", 0, "1 = 4-chunk K slices + block-tile patch kernels for 128 / 64-column problems")         \
+  X(fwd_n112, "TDG_FWD_N112", SW_UNSET, "112-column tiles of under-filled grids: 0 = never, 1 = 128-row tiles only")         \
+  X(ws128, "TDG_WS128", 1, "0 = only the 192-row LDS-DMA tile is wave-specialised")                                          \
+  X(wdma, "TDG_WDMA", 1, "0 = register-staged filter-gradient kernel")                                                       \
+  X(wdma_slowa, "TDG_WDMA_SLOWA", SW_UNSET, "set = the LDS-DMA filter gradient's general loader (mode 0)")                   \
+  X(wpatch, "TDG_WPATCH", 1, "0 = slab filter-gradient kernel instead of the patch-resident one")                            \
+  X(wpatch_nw, "TDG_WPATCH_NW", 8, "4 = the patch-resident filter gradient's one-wave-per-SIMD form")
+// Diagnostic library (build.sh stamps) only, per call: their results are garbage.
+#define CONV_SWITCHES_STAMPS(X)                                                                                              \
+  X(debug_ablate, "TDG_DEBUG_ABLATE", 0, "loop ablations: 1 no global loads in the loop, 2 + no LDS stores, 3 no MFMA")      \
+  X(patch_abl, "TDG_PATCH_ABL", 0, "1 .. 4 = the ablation instantiations of igemm_fwd_patch_kernel<192, 208>")
+
+struct ConvSwitches {
+#define X(field, var, unset, meaning) int field;
+  CONV_SWITCHES_ONCE(X)
+  CONV_SWITCHES_CALL(X)
+#ifdef TDG_STAMPS
+  CONV_SWITCHES_STAMPS(X)
+#endif
+#undef X
+  double eff[3];          // TDG_EFF=a,b,c (per call): relative efficiency of the 256 / 192 / 128-row tiles in the row-tile cost model
+};
+
+ConvSwitches conv_switches() {
+#define X(field, var, unset, meaning) s.field = getenv(var) ? atoi(getenv(var)) : unset;
+  static const ConvSwitches once = [] {
+    ConvSwitches s{};
+    CONV_SWITCHES_ONCE(X)
+    return s;
+  }();
+  ConvSwitches s = once;
+  CONV_SWITCHES_CALL(X)
+#ifdef TDG_STAMPS
+  CONV_SWITCHES_STAMPS(X)
+#endif
+#undef X
+  s.eff[0] = 0.72; s.eff[1] = 1.0; s.eff[2] = 0.83;   // measured in the step: 800-850 / 1140 (wave-specialised) / 950-980 TF
+  if (const char* e = getenv("TDG_EFF")) sscanf(e, "%lf,%lf,%lf", &s.eff[0], &s.eff[1], &s.eff[2]);
+  return s;
+}
+
 #ifdef TDG_STAMPS
 // diagnostic library only: where the stamping kernels write their per-wave cycle sums
 inline unsigned long long* stamp_ptr() {
@@ -3382,58 +3456,73 @@ void grant_col_partial(IgArgs& a, const TdgEpilogue* epi) {
   *epi->col_nblk_out = nblk;
 }
 
+// A kernel variant's name as the profiler prints it.  tdg_note_kernel keeps the pointer, so every distinct name (a fixed
+// set of fewer than 100) is formatted into this thread's table once and stays there.
+const char* kept_name(const char* fmt, ...) {
+  static thread_local char names[128][64];
+  static thread_local int n_names = 0;
+  char text[64];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(text, sizeof(text), fmt, ap);
+  va_end(ap);
+  for (int i = 0; i < n_names; ++i)
+    if (!strcmp(names[i], text)) return names[i];
+  if (n_names == 128) return "conv kernel";
+  return strcpy(names[n_names++], text);
+}
+
+// ---- a forward-type GEMM launch (conv forward, backward data by parity classes): the kernel variant it takes ------------
+// choose_fwd fills a FwdChoice and launches nothing; launch_fwd maps a choice to its template instantiation.
+enum { FWD_STAGED, FWD_DMA, FWD_PATCH, FWD_BP };   // igemm_fwd_kernel, igemm_fwd_dma_kernel, igemm_fwd_patch_kernel, igemm_fwd_bp_kernel
+struct FwdChoice {
+  int rc;                        // TDG_OK, or why nothing can be launched
+  int family, dtype;
+  bool veca;                     // FWD_STAGED: 16-byte vector gather
+  int bm, bn;                    // row and column tile
+  int ns;                        // ring stages (FWD_STAGED: 0)
+  int ws;                        // FWD_DMA wave layout: 1 = 4 loader + 4 compute waves, 0 = every wave loads and computes
+  int ck, pieces, lag;           // FWD_PATCH, FWD_BP: chunks per patch pixel, 1 KiB pieces per patch buffer, lagged loader schedule
+  int abl;                       // diagnostic library: TDG_PATCH_ABL instantiation of the 192-row patch tile
+  int ksplit, steps_per_split;   // FWD_DMA split-K (1: none)
+  size_t lds;                    // dynamic LDS of a workgroup
+};
+
+const char* fwd_choice_name(const FwdChoice& c) {
+  const char* t = c.dtype == TDG_BF16 ? "bf16" : "f32";
+  switch (c.family) {
+    case FWD_STAGED: return kept_name("igemm_fwd_kernel<%s,%d,%d>", t, c.bm, c.bn);
+    case FWD_DMA: return kept_name(c.ws ? "igemm_fwd_dma_kernel<%s,%d,%d,%d,8,1>" : "igemm_fwd_dma_kernel<%s,%d,%d,%d>", t, c.bm, c.bn, c.ns);
+    case FWD_PATCH:
+      // (the 128-row tile's diagnostic / fallback forms name their patch pieces and ring stages; the default form keeps the plain name)
+      if (c.bm == 128 && c.bn == 208 && (c.pieces != 12 || c.ns != 4))
+        return kept_name("igemm_fwd_patch_kernel<bf16,%d,%d,%d,%d>", c.bm, c.bn, c.pieces, c.ns);
+      return kept_name("igemm_fwd_patch_kernel<bf16,%d,%d>", c.bm, c.bn);
+    default: return kept_name("igemm_fwd_bp_kernel<bf16,256,%d>", c.bn);
+  }
+}
+
 template <typename T, int BM, int BN, int WGM, int WGN>
-int launch_fwd_cfg(const IgArgs& a, bool veca, int grid_x, double flops, hipStream_t s) {
-  const size_t lds = (size_t)(BM + BN) * IG_BKB + IG_MAX_TAPS * sizeof(int);
-  const dim3 grid(grid_x, 1, a.nclasses), block(256);
-  const char* name = TDG_NAME("igemm_fwd_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BM, BN);
-  return tdg_launch(name, 0, flops, s, [&] {
-    if (veca)
-      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, true>), grid, block, lds, s, a);
+int run_fwd_staged(const IgArgs& a, const FwdChoice& c, double flops, hipStream_t s) {
+  const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(256);
+  return tdg_launch(fwd_choice_name(c), 0, flops, s, [&] {
+    if (c.veca)
+      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, true>), grid, block, c.lds, s, a);
     else
-      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, false>), grid, block, lds, s, a);
+      hipLaunchKernelGGL((igemm_fwd_kernel<T, BM, BN, WGM, WGN, false>), grid, block, c.lds, s, a);
   });
 }
 
-template <typename T, int BM, int BN, int NS, int NW = 8, int WS = 0>
-int launch_fwd_dma(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
-  a.n_begin = 0;
-  a.ntiles_n = tdg_ceil_div(a.N, BN);
-  a.ntiles_m_max = tdg_ceil_div(mmax, BM);
-  if (sizeof(T) == 2 && !a.accumulate && (a.N & 3) == 0) grant_col_partial(a, epi);
+template <typename T, int BM, int BN, int NS, int WS = 0>
+int run_fwd_dma(const IgArgs& a, const FwdChoice& c, double flops, hipStream_t s) {
   constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
-  const size_t lds = NS * (size_t)(BM + BNL) * IG_BKB + IG_MAX_TAPS * sizeof(int) + BNL * sizeof(float);   // ring, taps, bias row
   static_assert(NS * (size_t)(BM + BNL) * IG_BKB + IG_MAX_TAPS * sizeof(int) + BNL * sizeof(float) <= 160 * 1024, "LDS budget");
-  // split-K: a grid that leaves most of the chip idle (pix2pix's 1x1 ... 8x8 bottleneck layers: 4 - 32 workgroups, each
-  // walking 128 - 256 K steps) is cut along K into f32 partial tiles, finished by splitk_finish_kernel
-  a.slab_rows = a.ntiles_m_max * BM;
-  int smax = 0;
-  for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
-  const long long wgs = (long long)a.ntiles_n * a.ntiles_m_max * a.nclasses;
-  const int ks_force = getenv("TDG_KSPLIT") ? atoi(getenv("TDG_KSPLIT")) : 0;                  // diagnostics: 1 = never, n = n splits
-  if (!WS && epi && epi->splitk_ws && epi->splitk_ws_bytes && wgs <= 128 && smax >= 16 && ks_force != 1) {
-    int want = (int)(256 / wgs);
-    if (want > smax / 4) want = smax / 4;                    // >= 4 steps per split
-    if (want > 8) want = 8;                                  // measured (64 images, 512 -> 512, 4x4 s2): 2x2 / 4x4 inputs 0.019 / 0.020 ms at 8 splits, 0.026 / 0.032 at 32
-    if (ks_force > 1) want = ks_force;
-    const int per = tdg_ceil_div(smax, want);
-    const int nsplit = tdg_ceil_div(smax, per);
-    const size_t need = (size_t)nsplit * a.nclasses * a.slab_rows * a.N * sizeof(float);
-    if (nsplit > 1 && need <= epi->splitk_ws_bytes) {
-      a.ksplit = nsplit;
-      a.steps_per_split = per;
-      a.slab = static_cast<float*>(epi->splitk_ws);
-      a.col_partial = nullptr;                               // (the partial tiles are not the stored tile)
-      if (epi->col_nblk_out) *epi->col_nblk_out = 0;
-    }
-  }
-  const dim3 grid(a.ntiles_n * a.ntiles_m_max, a.ksplit, a.nclasses), block(64 * NW);
-  const char* name = TDG_NAME(WS ? "igemm_fwd_dma_kernel<%s,%d,%d,%d,8,1>" : (NW == 8 ? "igemm_fwd_dma_kernel<%s,%d,%d,%d>" : "igemm_fwd_dma_kernel<%s,%d,%d,%d,4,0>"), sizeof(T) == 2 ? "bf16" : "f32", BM, BN, NS);
-  return tdg_launch<igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>>(name, (int)lds, flops, s, [&] {
-    hipLaunchKernelGGL((igemm_fwd_dma_kernel<T, BM, BN, NS, NW, WS>), grid, block, lds, s, a);
+  const dim3 grid(a.ntiles_n * a.ntiles_m_max, a.ksplit, a.nclasses), block(512);
+  return tdg_launch<igemm_fwd_dma_kernel<T, BM, BN, NS, 8, WS>>(fwd_choice_name(c), (int)c.lds, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_fwd_dma_kernel<T, BM, BN, NS, 8, WS>), grid, block, c.lds, s, a);
     if (a.ksplit > 1) {
       int mmx = 0;
-      for (int c = 0; c < a.nclasses; ++c) mmx = a.cls[c].M > mmx ? a.cls[c].M : mmx;
+      for (int i = 0; i < a.nclasses; ++i) mmx = a.cls[i].M > mmx ? a.cls[i].M : mmx;
       const long long items = (long long)mmx * ((a.N + 3) / 4);
       hipLaunchKernelGGL((splitk_finish_kernel<T>), dim3((unsigned)((items + 255) / 256), 1, a.nclasses), dim3(256), 0, s, a);
     }
@@ -3441,19 +3530,19 @@ int launch_fwd_dma(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hi
 }
 
 // igemm_fwd_patch_kernel: does it apply to this launch?  Fills the tap groups / lattice of every class when it does.
-// Conditions (each one is what the kernel's indexing assumes): bf16 vector gather, CK-chunk K slices, BN-column tiles with
+// Conditions (each one is what the kernel's indexing assumes): bf16 vector gather, ck-chunk K slices, bn-column tiles with
 // the staged epilogue, row tiles of whole images OR of one bh x bw block of an image's anchor grid (then the classes' GH, GW,
 // fd_ghw, fd_gw are rewritten to the block's and nbh, nbw, halo set -- only when the whole plan holds), a source whose
-// sub-lattices all have the same shape, patches that fit PIECES KiB, tap groups in K order, and a phase schedule in which
-// every patch lands two steps before its first read (the loader's own rule, simulated here).  LAG = 1: the 4-stage ring's
+// sub-lattices all have the same shape, patches that fit `pieces` KiB, tap groups in K order, and a phase schedule in which
+// every patch lands two steps before its first read (the loader's own rule, simulated here).  lag = 1: the 4-stage ring's
 // schedule, in which the loaders' wait runs one step behind their issue and a two-step patch load is visible one step later.
-template <int BM, int BN = 208, int CK = PT_CK, int PIECES = PT_PIECES, bool FORCE_HALO = false, int LAG = 0>
-bool plan_fwd_patch(IgArgs& a, int mmax) {
-  const int enabled = getenv("TDG_PATCH") ? atoi(getenv("TDG_PATCH")) : 1;     // diagnostics: 0 = igemm_fwd_dma_kernel, 2 = also on small grids
-  if (!enabled || (int)a.fd_ck.d != CK || a.accumulate || (a.N & 3) || (a.Cso & 3)) return false;
+// enabled: ConvSwitches.patch.
+bool plan_fwd_patch(IgArgs& a, int mmax, int enabled, int bm, int bn = 208, int ck = PT_CK, int pieces = PT_PIECES, bool force_halo = false,
+                    int lag = 0) {
+  if (!enabled || (int)a.fd_ck.d != ck || a.accumulate || (a.N & 3) || (a.Cso & 3)) return false;
   if (a.sigma < 1 || a.sigma > 2 || a.SH % a.sigma || a.SW % a.sigma) return false;
   const int LH = a.SH / a.sigma, LWd = a.SW / a.sigma;        // the source's sub-lattice
-  if (enabled != 2 && (long long)tdg_ceil_div(mmax, BM) * tdg_ceil_div(a.N, BN) * a.nclasses < 160) return false;   // small grids: the 112-column forms
+  if (enabled != 2 && (long long)tdg_ceil_div(mmax, bm) * tdg_ceil_div(a.N, bn) * a.nclasses < 160) return false;   // small grids: the 112-column forms
   struct Geo { int bh, bw, nbh, nbw, halo, QH, QW; } geo[IG_MAX_CLASSES];
   for (int ci = 0; ci < a.nclasses; ++ci) {
     IgClass& c = a.cls[ci];
@@ -3479,27 +3568,27 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
     }
     c.ngroups = ng;
     Geo& g = geo[ci];
-    if (BM % ghw == 0 && !(FORCE_HALO && ghw == BM)) {         // whole images: the patch is the image's sub-lattice, taps outside it are masked
+    if (bm % ghw == 0 && !(force_halo && ghw == bm)) {         // whole images: the patch is the image's sub-lattice, taps outside it are masked
       g = Geo{c.GH, c.GW, 1, 1, 0, LH, LWd};
     } else {                                                   // a block of one image with a halo of dmax lattice pixels
       int bw = c.GW < 16 ? c.GW : 16;
-      while (bw > 1 && (c.GW % bw || BM % bw)) --bw;
-      const int bh = BM / bw;
-      if (bh * bw != BM || c.GH % bh || c.GW % bw) return false;
+      while (bw > 1 && (c.GW % bw || bm % bw)) --bw;
+      const int bh = bm / bw;
+      if (bh * bw != bm || c.GH % bh || c.GW % bw) return false;
       g = Geo{bh, bw, c.GH / bh, c.GW / bw, dmax, bh + 2 * dmax, bw + 2 * dmax};
     }
     if (g.QW > 32 || g.QH > 64) return false;
-    if ((BM / (g.bh * g.bw)) * g.QH * g.QW * PT_PIXB > PIECES * 1024 || g.bh > g.QH + 8 || g.bw > g.QW + 8) return false;
+    if ((bm / (g.bh * g.bw)) * g.QH * g.QW * PT_PIXB > pieces * 1024 || g.bh > g.QH + 8 || g.bw > g.QW + 8) return false;
     for (int t = 0; t < c.ntaps; ++t) {
       const int dh = (signed char)(c.tap[t] & 0xff), dw = (signed char)((c.tap[t] >> 8) & 0xff);
       const int ph = ((dh % a.sigma) + a.sigma) % a.sigma, pw = ((dw % a.sigma) + a.sigma) % a.sigma;
       const int off = ((dh - ph) / a.sigma) * g.QW + (dw - pw) / a.sigma;
       if (off < -127 || off > 127) return false;
     }
-    // the loader's schedule: phase p (>= PT_NPB) is issued in steps s_p, s_p + 1 and is visible from step s_p + 3 (+ LAG)
-    const int P = a.nslices * ng, slc = c.ntaps * CK;
-    auto first_chunk = [&](int p) { return (p / ng) * slc + c.grp[p % ng].t0 * CK; };
-    auto end_chunk = [&](int p) { return (p / ng) * slc + (c.grp[p % ng].t0 + c.grp[p % ng].nt) * CK; };
+    // the loader's schedule: phase p (>= PT_NPB) is issued in steps s_p, s_p + 1 and is visible from step s_p + 3 (+ lag)
+    const int P = a.nslices * ng, slc = c.ntaps * ck;
+    auto first_chunk = [&](int p) { return (p / ng) * slc + c.grp[p % ng].t0 * ck; };
+    auto end_chunk = [&](int p) { return (p / ng) * slc + (c.grp[p % ng].t0 + c.grp[p % ng].nt) * ck; };
     // patches 1 .. PT_NPB - 1 go out whole in steps 0 .. PT_NPB - 2 (visible to the reads of step issue + 2); the lagged form
     // issues each a step earlier -- patch 1 in the prologue -- and sees it a step later: the same rule
     for (int p = 1; p < PT_NPB && p < P; ++p)
@@ -3508,7 +3597,7 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
     for (int p = PT_NPB; p < P; ++p) {
       const int ready = (end_chunk(p - PT_NPB) - 1) / 8 + 1;
       const int issue = ready > prev_issue + 2 ? ready : prev_issue + 2;
-      if (first_chunk(p) / 8 < issue + 3 + LAG) return false;
+      if (first_chunk(p) / 8 < issue + 3 + lag) return false;
       prev_issue = issue;
     }
   }
@@ -3526,64 +3615,47 @@ bool plan_fwd_patch(IgArgs& a, int mmax) {
   return true;
 }
 
-// LDS of one igemm_fwd_patch_kernel workgroup: zero pixel, NS ring stages, the patch buffers, 64 bytes of chunk table per K step
-// of the longest class, the bias row
-template <int BN, int PIECES, int NS>
-size_t fwd_patch_lds(const IgArgs& a) {
+inline int max_steps(const IgArgs& a) {
   int smax = 0;
   for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
-  constexpr int BNL = 2 * ((BN / 16 + 1) / 2) * 16;
-  return PT_ZEROB + NS * (size_t)BNL * IG_BKB + PT_NPB * (size_t)PIECES * 1024 + (size_t)smax * 64 + BNL * sizeof(float);
+  return smax;
 }
 
-template <int BM, int BN, int CK = PT_CK, int PIECES = PT_PIECES, int NS = 3>
-int launch_fwd_patch(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
-  a.n_begin = 0;
-  a.ntiles_n = tdg_ceil_div(a.N, BN);
-  a.ntiles_m_max = tdg_ceil_div(mmax, BM);
-  grant_col_partial(a, epi);
-  const size_t lds = fwd_patch_lds<BN, PIECES, NS>(a);
-  if (lds > 160 * 1024) {
-    tdg_set_error("igemm_fwd_patch: %zu bytes of LDS", lds);
-    return TDG_EUNSUPPORTED;
-  }
+// LDS of one igemm_fwd_patch_kernel workgroup: zero pixel, ns ring stages, the patch buffers, 64 bytes of chunk table per K step
+// of the longest class, the bias row
+inline size_t fwd_patch_lds(int smax, int bn, int pieces, int ns) {
+  const int bnl = 2 * ((bn / 16 + 1) / 2) * 16;
+  return PT_ZEROB + ns * (size_t)bnl * IG_BKB + PT_NPB * (size_t)pieces * 1024 + (size_t)smax * 64 + bnl * sizeof(float);
+}
+
+template <int BM, int BN, int CK, int PIECES, int NS, int ABL = 0>
+int run_fwd_patch(const IgArgs& a, const FwdChoice& c, double flops, hipStream_t s) {
   const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
-  // (the 128-row tile's diagnostic / fallback forms name their patch pieces and ring stages; the default form keeps the plain name)
-  const char* name = BM == 128 && BN == 208 && (PIECES != 12 || NS != 4) ? TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d,%d,%d>", BM, BN, PIECES, NS)
-                                                                       : TDG_NAME("igemm_fwd_patch_kernel<bf16,%d,%d>", BM, BN);
-  auto go = [&](auto abl) {
-    constexpr int ABL = decltype(abl)::value;
-    return tdg_launch<igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>>(name, 160 * 1024, flops, s, [&] {
-      hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>), grid, block, lds, s, a);
-    });
-  };
-#ifdef TDG_STAMPS
-  // ablation instantiations (their results are garbage): compiled into the diagnostic library (build.sh stamps) only
-  if constexpr (BM == 192) {
-    const int abl = getenv("TDG_PATCH_ABL") ? atoi(getenv("TDG_PATCH_ABL")) : 0;
-    if (abl == 1) return go(IntC<1>{});
-    if (abl == 2) return go(IntC<2>{});
-    if (abl == 3) return go(IntC<3>{});
-    if (abl == 4) return go(IntC<4>{});
-  }
-#endif
-  return go(IntC<0>{});
+  return tdg_launch<igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>>(fwd_choice_name(c), 160 * 1024, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_fwd_patch_kernel<BM, BN, ABL, CK, PIECES, NS>), grid, block, c.lds, s, a);
+  });
+}
+
+inline FwdChoice fwd_tile(int family, int bm, int bn, int ns, int ws = 0, int ck = 0, int pieces = 0, int lag = 0) {
+  FwdChoice c;
+  memset(&c, 0, sizeof(c));
+  c.family = family; c.bm = bm; c.bn = bn; c.ns = ns; c.ws = ws; c.ck = ck; c.pieces = pieces; c.lag = lag;
+  return c;
 }
 
 // The 128-row tile of igemm_fwd_patch_kernel.  Its patch is 128 lattice pixels x 80 B = 10 KB whatever the geometry (2 images of
 // an 8 x 8 lattice, 8 of a 4 x 4 one), so it takes 12-piece patch buffers, and the 16 KB they free pay for a fourth ring stage:
 // the lagged loader schedule (igemm_fwd_patch_kernel, NS = 4) where 152 704 + 64 x K steps fit the 160 KB (<= 174 steps),
-// the 3-stage form beyond.  TDG_PATCH128 (diagnostics): 0 = the form this one replaced (16 pieces, 3 stages), 1 = 12 pieces, 3
-// stages.  Every form multiplies the same fragments in the same order: the results are bit-equal.  False: no plan applies, nothing launched.
-inline bool launch_fwd_patch128(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s, int* rc) {
-  const int form = getenv("TDG_PATCH128") ? atoi(getenv("TDG_PATCH128")) : 2;
+// the 3-stage form beyond.  ConvSwitches.patch128: 0 = the form this one replaced (16 pieces, 3 stages), 1 = 12 pieces, 3
+// stages.  Every form multiplies the same fragments in the same order: the results are bit-equal.  False: no plan applies.
+bool choose_fwd_patch128(IgArgs& a, int mmax, const ConvSwitches& sw, FwdChoice* c) {
   constexpr int P128 = 12;
-  if (form >= 2 && fwd_patch_lds<208, P128, 4>(a) <= 160 * 1024 && plan_fwd_patch<128, 208, PT_CK, P128, false, 1>(a, mmax))
-    *rc = launch_fwd_patch<128, 208, PT_CK, P128, 4>(a, mmax, flops, epi, s);
-  else if (form >= 1 && plan_fwd_patch<128, 208, PT_CK, P128>(a, mmax))
-    *rc = launch_fwd_patch<128, 208, PT_CK, P128>(a, mmax, flops, epi, s);
-  else if (plan_fwd_patch<128>(a, mmax))
-    *rc = launch_fwd_patch<128, 208>(a, mmax, flops, epi, s);
+  if (sw.patch128 >= 2 && fwd_patch_lds(max_steps(a), 208, P128, 4) <= 160 * 1024 && plan_fwd_patch(a, mmax, sw.patch, 128, 208, PT_CK, P128, false, 1))
+    *c = fwd_tile(FWD_PATCH, 128, 208, 4, 1, PT_CK, P128, 1);
+  else if (sw.patch128 >= 1 && plan_fwd_patch(a, mmax, sw.patch, 128, 208, PT_CK, P128))
+    *c = fwd_tile(FWD_PATCH, 128, 208, 3, 1, PT_CK, P128);
+  else if (plan_fwd_patch(a, mmax, sw.patch, 128))
+    *c = fwd_tile(FWD_PATCH, 128, 208, 3, 1, PT_CK, PT_PIECES);
   else
     return false;
   return true;
@@ -3592,12 +3664,10 @@ inline bool launch_fwd_patch128(IgArgs& a, int mmax, double flops, const TdgEpil
 // igemm_fwd_bp_kernel: the block-patch plan (on a copy: the classes are rewritten only when everything holds) plus what the
 // all-wave kernel assumes on top: one 16 x 16 block per row tile with a halo'd patch, tap groups of exactly four, a K of whole
 // two-step phases.
-template <int BN>
-bool plan_fwd_bp(IgArgs& a, int mmax) {
-  const char* e = getenv("TDG_BP");                         // variant tests: 0 = the 4 + 4 wave-specialised patch kernel
-  if (e && atoi(e) == 0) return false;
+bool plan_fwd_bp(IgArgs& a, int mmax, const ConvSwitches& sw, int bn) {
+  if (sw.bp == 0) return false;
   IgArgs t = a;
-  if (!plan_fwd_patch<256, BN, 4, BP_PIECES, true>(t, mmax)) return false;
+  if (!plan_fwd_patch(t, mmax, sw.patch, 256, bn, 4, BP_PIECES, true)) return false;
   for (int ci = 0; ci < t.nclasses; ++ci) {
     const IgClass& c = t.cls[ci];
     if (c.GH * c.GW != 256 || c.halo < 1 || c.QH * c.QW * PT_PIXB > BP_PIECES * 1024) return false;
@@ -3611,134 +3681,88 @@ bool plan_fwd_bp(IgArgs& a, int mmax) {
 }
 
 template <int BN>
-int launch_fwd_bp(IgArgs& a, int mmax, double flops, const TdgEpilogue* epi, hipStream_t s) {
-  a.n_begin = 0;
-  a.ntiles_n = tdg_ceil_div(a.N, BN);
-  a.ntiles_m_max = tdg_ceil_div(mmax, 256);
-  grant_col_partial(a, epi);
-  int smax = 0;
-  for (int c = 0; c < a.nclasses; ++c) smax = a.cls[c].nsteps > smax ? a.cls[c].nsteps : smax;
-  const size_t lds = PT_ZEROB + 3 * (size_t)BN * IG_BKB + PT_NPB * (size_t)BP_PIECES * 1024 + 1024 + (size_t)smax * 8 + BN * sizeof(float);
-  if (lds > 160 * 1024) {
-    tdg_set_error("igemm_fwd_bp: %zu bytes of LDS", lds);
-    return TDG_EUNSUPPORTED;
-  }
-#ifdef TDG_STAMPS
-  a.stamps = stamp_ptr();
-#endif
+int run_fwd_bp(const IgArgs& a, const FwdChoice& c, double flops, hipStream_t s) {
   const dim3 grid(a.ntiles_n * a.ntiles_m_max, 1, a.nclasses), block(512);
-  return tdg_launch<igemm_fwd_bp_kernel<BN>>(TDG_NAME("igemm_fwd_bp_kernel<bf16,256,%d>", BN), 160 * 1024, flops, s, [&] {
-    hipLaunchKernelGGL((igemm_fwd_bp_kernel<BN>), grid, block, lds, s, a);
+  return tdg_launch<igemm_fwd_bp_kernel<BN>>(fwd_choice_name(c), 160 * 1024, flops, s, [&] {
+    hipLaunchKernelGGL((igemm_fwd_bp_kernel<BN>), grid, block, c.lds, s, a);
   });
 }
 
-template <typename T>
-int launch_fwd(IgArgs& a, bool veca, int bn, double flops, const TdgEpilogue* epi, hipStream_t s) {
-  constexpr int BM = 128;
-#ifdef TDG_STAMPS
-  static const int dbg = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;   // loop ablations (garbage results): diagnostic library only
-#else
-  const int dbg = 0;
-#endif
-  const char* dma_env = getenv("TDG_DMA");          // diagnostics: 0 = never, 3 / 4 = force the 192 / 256-row tile
-  const int dma_mode = dma_env ? atoi(dma_env) : 1;
-  a.debug = dbg;
-#ifdef TDG_STAMPS
-  a.stamps = stamp_ptr();
-#endif
-  int mmax = 0;
-  for (int c = 0; c < a.nclasses; ++c) mmax = a.cls[c].M > mmax ? a.cls[c].M : mmax;
+// Family and tile of a launch whose longest class has mmax rows.  A patch plan that holds commits its geometry into `a`.
+FwdChoice choose_fwd_tile(IgArgs& a, bool veca, int bn, bool bf16, int mmax, const ConvSwitches& sw) {
+  const bool patch_ok = bf16 && veca && sw.dma == 1 && sw.dma_bm == SW_UNSET && sw.dma_nw == SW_UNSET;
+  const bool dma_ok = veca && sw.dma && (a.N & 3) == 0 && (a.Cso & 3) == 0;
   // large problems: 256-row tiles fed by LDS-DMA (needs >= ~1 workgroup per CU to pay off)
   // 208-column problems with a vector gather always take the LDS-DMA kernel (measured faster than the
   // register-staged one even when the grid does not fill the chip)
-  if constexpr (sizeof(T) == 2) {
+  if (patch_ok && bn == 208) {
     // whole-image row tiles with the gathered operand resident in LDS (igemm_fwd_patch_kernel), 192 or 128 rows: the
     // same cost model as below (rounds of 256 one-per-CU workgroups x rows per tile / relative efficiency; measured on the
     // 1536-image GEMMs: 8 - 13 % less time than igemm_fwd_dma_kernel's 192-row form)
-    if (veca && bn == 208 && dma_mode == 1 && !getenv("TDG_DMA_BM") && !getenv("TDG_DMA_NW")) {
-      const long long per = (long long)tdg_ceil_div(a.N, 208) * a.nclasses;
-      const double c192 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 192), 256) * 192 / 1.0;
-      // 0.78: what the rounds model needs at the shapes where the two tiles compete, measured in the step with the lagged
-      // 128-row form.  On whole-round launches that form now runs 1 096 - 1 124 TF against the 192-row tile's 1 158 - 1 183
-      // (0.95; it was 0.75), but 0.95 was built and measured: c3 forward at 2 560 images (5 rounds x 128 rows against 4 x 192)
-      // moved to 128 rows and took 166 instead of 156 us (implied 0.78), the two 1 024-image c2 launches (4 x 128 against
-      // 3 x 192) moved and tied at 259 us (implied 0.89), the step 16.45 - 16.49 against 16.43 - 16.50 ms.  Not kept.  More,
-      // smaller tiles pay the ~13 000 clocks outside the K loop and the filter intake more often than the K step's rate
-      // shows.  With 0.78 no launch of the GAN step changes its row tile.
-      const double c128 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 128), 256) * 128 / 0.78;
-      const int pbm = getenv("TDG_PATCH_BM") ? atoi(getenv("TDG_PATCH_BM")) : 0;            // diagnostics: force a row tile
-      const bool want128 = pbm ? pbm == 128 : c128 < c192 - 1e-9;
-      int rc = TDG_OK;
-      if (want128 && launch_fwd_patch128(a, mmax, flops, epi, s, &rc)) return rc;
-      if (plan_fwd_patch<192>(a, mmax)) return launch_fwd_patch<192, 208>(a, mmax, flops, epi, s);
-      if (!want128 && !pbm && launch_fwd_patch128(a, mmax, flops, epi, s, &rc)) return rc;
-    }
+    const long long per = (long long)tdg_ceil_div(a.N, 208) * a.nclasses;
+    const double c192 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 192), 256) * 192 / 1.0;
+    // 0.78: what the rounds model needs at the shapes where the two tiles compete, measured in the step with the lagged
+    // 128-row form.  On whole-round launches that form now runs 1 096 - 1 124 TF against the 192-row tile's 1 158 - 1 183
+    // (0.95; it was 0.75), but 0.95 was built and measured: c3 forward at 2 560 images (5 rounds x 128 rows against 4 x 192)
+    // moved to 128 rows and took 166 instead of 156 us (implied 0.78), the two 1 024-image c2 launches (4 x 128 against
+    // 3 x 192) moved and tied at 259 us (implied 0.89), the step 16.45 - 16.49 against 16.43 - 16.50 ms.  Not kept.  More,
+    // smaller tiles pay the ~13 000 clocks outside the K loop and the filter intake more often than the K step's rate
+    // shows.  With 0.78 no launch of the GAN step changes its row tile.
+    const double c128 = (double)tdg_ceil_div(per * tdg_ceil_div(mmax, 128), 256) * 128 / 0.78;
+    const int pbm = sw.patch_bm;
+    const bool want128 = pbm ? pbm == 128 : c128 < c192 - 1e-9;
+    FwdChoice c;
+    if (want128 && choose_fwd_patch128(a, mmax, sw, &c)) return c;
+    if (plan_fwd_patch(a, mmax, sw.patch, 192)) return fwd_tile(FWD_PATCH, 192, 208, 3, 1, PT_CK, PT_PIECES);
+    if (!want128 && !pbm && choose_fwd_patch128(a, mmax, sw, &c)) return c;
   }
-  if (veca && bn == 208 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0) {
+  if (dma_ok && bn == 208) {
     // one 8-wave workgroup per CU.  Row tiles: 256 (2-stage LDS ring), 192 and 128 (3-stage ring, loads two
     // steps ahead).  (Covering 400 = 208 + 192 / 800 = 2 x 208 + 2 x 192 columns exactly with a second launch of
     // 192-wide tiles -- 26 / 52 column tiles of 16 instead of 28 / 56 -- was measured: -1..-4 % on the 1536-image
     // GEMMs, +9 % on c3 backward-data and up to +70 % wherever a launch no longer fills the chip.  Not kept.)
-    // Cost model for the row tile: rounds of 256 workgroups x rows per tile / measured relative efficiency.
+    // Cost model for the row tile: rounds of 256 workgroups x rows per tile / measured relative efficiency (ConvSwitches.eff).
     const long long per = (long long)tdg_ceil_div(a.N, 208) * a.nclasses;
-    static const int force = getenv("TDG_DMA_BM") ? atoi(getenv("TDG_DMA_BM")) : 0;   // diagnostics
     const int bms[3] = {256, 192, 128};
-    double eff[3] = {0.72, 1.0, 0.83};                // measured in the step: 800-850 / 1140 (wave-specialised) / 950-980 TF
-    if (const char* e = getenv("TDG_EFF")) sscanf(e, "%lf,%lf,%lf", &eff[0], &eff[1], &eff[2]);   // diagnostics
     int best = 0;
     double best_cost = 1e30;
     for (int i = 0; i < 3; ++i) {
       const long long tiles = per * tdg_ceil_div(mmax, bms[i]);
-      const double cost = (double)tdg_ceil_div(tiles, 256) * bms[i] / eff[i];
+      const double cost = (double)tdg_ceil_div(tiles, 256) * bms[i] / sw.eff[i];
       if (cost < best_cost - 1e-9) { best_cost = cost; best = i; }
     }
-    int bm = force ? force : bms[best];
-    if (dma_mode == 3) bm = 192;
-    if (dma_mode == 4) bm = 256;
-    static const int ring192 = getenv("TDG_RING") ? atoi(getenv("TDG_RING")) : 3;     // diagnostics: 2 = 2-stage ring on the 192-row tile
+    int bm = sw.dma_bm != SW_UNSET && sw.dma_bm ? sw.dma_bm : bms[best];
+    if (sw.dma == 3) bm = 192;
+    if (sw.dma == 4) bm = 256;
     // (a 64-row tile, two workgroups per CU, was tried for the 4-step c1 forward: no change -- with K padded 75 -> 256
     //  and N 200 -> 224 that GEMM is bound by its padded MFMA work, not by serialised prologue / epilogue phases)
+    const bool specialised = bf16 && !a.accumulate && (sw.dma_nw == SW_UNSET || sw.dma_nw == 44);
     if (bm == 128) {
       // a grid that leaves half of the CUs idle (the generator's 2x2 / 4x4 layers at batch 512: 64-128 workgroups)
       // takes 112-column tiles instead: twice the workgroups
-      const char* n112_env = getenv("TDG_FWD_N112");            // diagnostics: 0 = never, 1 = 128-row tiles only
-      if (per * tdg_ceil_div(mmax, 128) <= 128 && a.N > 112 && !(n112_env && atoi(n112_env) == 0)) {
+      if (per * tdg_ceil_div(mmax, 128) <= 128 && a.N > 112 && sw.fwd_n112 != 0) {
         const long long wg112 = (long long)tdg_ceil_div(a.N, 112) * a.nclasses * tdg_ceil_div(mmax, 128);
-        if (wg112 <= 128 && !(n112_env && atoi(n112_env) == 1)) return launch_fwd_dma<T, 64, 112, 3>(a, mmax, flops, epi, s);   // still half empty
-        return launch_fwd_dma<T, 128, 112, 3>(a, mmax, flops, epi, s);
+        if (wg112 <= 128 && sw.fwd_n112 != 1) return fwd_tile(FWD_DMA, 64, 112, 3);   // still half empty
+        return fwd_tile(FWD_DMA, 128, 112, 3);
       }
-      if constexpr (sizeof(T) == 2) {
-        const char* nw_env = getenv("TDG_DMA_NW");          // diagnostics: 8 = every wave loads and computes
-        const char* ws128_env = getenv("TDG_WS128");        // diagnostics: 0 = only the 192-row tile is specialised
-        if (!a.accumulate && !(nw_env && atoi(nw_env) != 44) && !(ws128_env && atoi(ws128_env) == 0))
-          return launch_fwd_dma<T, 128, 208, 3, 8, 1>(a, mmax, flops, epi, s);
-      }
-      return launch_fwd_dma<T, 128, 208, 3>(a, mmax, flops, epi, s);
+      return fwd_tile(FWD_DMA, 128, 208, 3, specialised && sw.ws128 != 0);
     }
     // 192-row tile, bf16, staged epilogue: the wave-specialised form (4 compute + 4 loader waves; measured +5 % on
-    // these launches inside the training step).  TDG_DMA_NW (diagnostics): 8 = every wave loads and computes
+    // these launches inside the training step)
     // (a four-wave form, one wave per SIMD, measured -17 %, is no longer instantiated)
-    const char* nw_env = getenv("TDG_DMA_NW");
-    const int nw192 = nw_env ? atoi(nw_env) : 44;
-    if constexpr (sizeof(T) == 2)
-      if (bm == 192 && nw192 == 44 && !a.accumulate && ring192 != 2) return launch_fwd_dma<T, 192, 208, 3, 8, 1>(a, mmax, flops, epi, s);
-    if (bm == 192) return ring192 == 2 ? launch_fwd_dma<T, 192, 208, 2>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 192, 208, 3>(a, mmax, flops, epi, s);
-    return launch_fwd_dma<T, 256, 208, 2>(a, mmax, flops, epi, s);
+    if (bm == 192) return sw.ring == 2 ? fwd_tile(FWD_DMA, 192, 208, 2) : fwd_tile(FWD_DMA, 192, 208, 3, specialised);
+    return fwd_tile(FWD_DMA, 256, 208, 2);
   }
   // 128-column problems (pix2pix / VAE widths 128, 256, 512, 1024) and 65..112 columns (the generator's 100-channel
   // layers, a 7-tile-wide column tile): the same LDS-DMA kernel, 3-stage ring at every row tile
   // 128- / 64-column problems whose K runs in 32-channel slices (pix2pix / VAE widths): 256-row tiles = four whole images or
   // one 16 x 16 block of an image, the gathered operand resident in LDS patches (igemm_fwd_patch_kernel<256, 128 | 64, 4-chunk
   // slices, 28 KiB patches>): 16 + 13 KB (128 columns) / 8 + 13 KB (64) of intake per K step instead of 16 + 32 / 8 + 16
-  if constexpr (sizeof(T) == 2) {
-    if (veca && dma_mode == 1 && (bn == 128 || bn == 64) && !getenv("TDG_DMA_BM") && !getenv("TDG_DMA_NW")) {
-      if (bn == 128 && a.N > 112 && plan_fwd_bp<128>(a, mmax)) return launch_fwd_bp<128>(a, mmax, flops, epi, s);
-      if (bn == 64 && a.N > 32 && plan_fwd_bp<64>(a, mmax)) return launch_fwd_bp<64>(a, mmax, flops, epi, s);
-      if (bn == 128 && a.N > 112 && plan_fwd_patch<256, 128, 4, 28>(a, mmax)) return launch_fwd_patch<256, 128, 4, 28>(a, mmax, flops, epi, s);
-      if (bn == 64 && a.N > 32 && plan_fwd_patch<256, 64, 4, 28>(a, mmax)) return launch_fwd_patch<256, 64, 4, 28>(a, mmax, flops, epi, s);
-    }
+  if (patch_ok && (bn == 128 ? a.N > 112 : bn == 64 && a.N > 32)) {
+    if (plan_fwd_bp(a, mmax, sw, bn)) return fwd_tile(FWD_BP, 256, bn, 3, 0, 4, BP_PIECES);
+    if (plan_fwd_patch(a, mmax, sw.patch, 256, bn, 4, 28)) return fwd_tile(FWD_PATCH, 256, bn, 3, 1, 4, 28);
   }
-  if (veca && bn == 128 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0) {
+  if (dma_ok && bn == 128) {
     const int bnt = a.N <= 112 ? 112 : 128;
     const long long per = (long long)tdg_ceil_div(a.N, bnt) * a.nclasses;
     const long long t256 = per * tdg_ceil_div(mmax, 256), t128 = per * tdg_ceil_div(mmax, 128);
@@ -3747,36 +3771,138 @@ int launch_fwd(IgArgs& a, bool veca, int bn, double flops, const TdgEpilogue* ep
     //  638 vs 709 TF (112 columns, the generator's dc3 at 2560 images): the smaller tile's intake per FLOP costs more than the
     //  overlap returns.  Not kept.)
     const double c256 = (double)tdg_ceil_div(t256, 256) * 256, c128 = (double)tdg_ceil_div(t128, 256) * 128 / 0.85;
-    if (bnt == 112) return c128 < c256 ? launch_fwd_dma<T, 128, 112, 3>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 256, 112, 3>(a, mmax, flops, epi, s);
-    return c128 < c256 ? launch_fwd_dma<T, 128, 128, 3>(a, mmax, flops, epi, s) : launch_fwd_dma<T, 256, 128, 3>(a, mmax, flops, epi, s);
+    return fwd_tile(FWD_DMA, c128 < c256 ? 128 : 256, bnt, 3);
   }
   // 64-column problems: 128-row tile (3 loader pieces per wave on 4 column tiles)
-  if (veca && bn == 64 && dma_mode && (a.N & 3) == 0 && (a.Cso & 3) == 0 && a.N > 32) return launch_fwd_dma<T, 128, 64, 3>(a, mmax, flops, epi, s);
-  a.ntiles_n = tdg_ceil_div(a.N, bn);
-  a.ntiles_m_max = tdg_ceil_div(mmax, BM);
-  int gx = a.ntiles_n * a.ntiles_m_max;
-  // under-filled chip (fewer than ~1.5 workgroups per CU): halve the row tile to double the grid
-  if (bn == 208 && (long long)gx * a.nclasses < 384) {
-    a.ntiles_m_max = tdg_ceil_div(mmax, 64);
-    gx = a.ntiles_n * a.ntiles_m_max;
-    return launch_fwd_cfg<T, 64, 208, 4, 1>(a, veca, gx, flops, s);
+  if (dma_ok && bn == 64 && a.N > 32) return fwd_tile(FWD_DMA, 128, 64, 3);
+  // the register-staged kernel; an under-filled chip (fewer than ~1.5 workgroups per CU) halves the row tile to double the grid
+  if (bn == 208 && (long long)tdg_ceil_div(a.N, 208) * tdg_ceil_div(mmax, 128) * a.nclasses < 384) return fwd_tile(FWD_STAGED, 64, 208, 0);
+  return fwd_tile(FWD_STAGED, 128, bn, 0);
+}
+
+// What every launcher needs of a chosen tile, in one place: the grid, the column partials, split-K and the LDS size.
+void place_fwd(IgArgs& a, FwdChoice& c, int mmax, const TdgEpilogue* epi, const ConvSwitches& sw) {
+  a.n_begin = 0;
+  a.ntiles_n = tdg_ceil_div(a.N, c.bn);
+  a.ntiles_m_max = tdg_ceil_div(mmax, c.bm);
+  c.ksplit = a.ksplit;
+  c.steps_per_split = a.steps_per_split;
+  const int smax = max_steps(a);
+  const int bnl = 2 * ((c.bn / 16 + 1) / 2) * 16;
+  if (c.family == FWD_STAGED) {                                // (no column partials from this kernel)
+    c.lds = (size_t)(c.bm + c.bn) * IG_BKB + IG_MAX_TAPS * sizeof(int);
+    return;
   }
-  switch (bn) {
-    case 16: return launch_fwd_cfg<T, BM, 16, 4, 1>(a, veca, gx, flops, s);
-    case 64: return launch_fwd_cfg<T, BM, 64, 4, 1>(a, veca, gx, flops, s);
-    case 128: return launch_fwd_cfg<T, BM, 128, 2, 2>(a, veca, gx, flops, s);
-    case 208: return launch_fwd_cfg<T, BM, 208, 4, 1>(a, veca, gx, flops, s);
+  if (c.family == FWD_PATCH || c.family == FWD_BP) {
+    grant_col_partial(a, epi);
+    c.lds = c.family == FWD_PATCH ? fwd_patch_lds(smax, c.bn, c.pieces, c.ns)
+                                  : PT_ZEROB + 3 * (size_t)c.bn * IG_BKB + PT_NPB * (size_t)BP_PIECES * 1024 + 1024 + (size_t)smax * 8 + c.bn * sizeof(float);
+    if (c.lds > 160 * 1024) {
+      tdg_set_error("%s: %zu bytes of LDS", c.family == FWD_PATCH ? "igemm_fwd_patch" : "igemm_fwd_bp", c.lds);
+      c.rc = TDG_EUNSUPPORTED;
+    }
+    return;
   }
-  tdg_set_error("igemm_fwd: no tile config for BN=%d", bn);
+  if (c.dtype == TDG_BF16 && !a.accumulate && (a.N & 3) == 0) grant_col_partial(a, epi);
+  c.lds = c.ns * (size_t)(c.bm + bnl) * IG_BKB + IG_MAX_TAPS * sizeof(int) + bnl * sizeof(float);   // ring, taps, bias row
+  // split-K: a grid that leaves most of the chip idle (pix2pix's 1x1 ... 8x8 bottleneck layers: 4 - 32 workgroups, each
+  // walking 128 - 256 K steps) is cut along K into f32 partial tiles, finished by splitk_finish_kernel
+  a.slab_rows = a.ntiles_m_max * c.bm;
+  const long long wgs = (long long)a.ntiles_n * a.ntiles_m_max * a.nclasses;
+  const int ks_force = sw.ksplit;
+  if (!c.ws && epi && epi->splitk_ws && epi->splitk_ws_bytes && wgs <= 128 && smax >= 16 && ks_force != 1) {
+    int want = (int)(256 / wgs);
+    if (want > smax / 4) want = smax / 4;                    // >= 4 steps per split
+    if (want > 8) want = 8;                                  // measured (64 images, 512 -> 512, 4x4 s2): 2x2 / 4x4 inputs 0.019 / 0.020 ms at 8 splits, 0.026 / 0.032 at 32
+    if (ks_force > 1) want = ks_force;
+    const int per = tdg_ceil_div(smax, want);
+    const int nsplit = tdg_ceil_div(smax, per);
+    const size_t need = (size_t)nsplit * a.nclasses * a.slab_rows * a.N * sizeof(float);
+    if (nsplit > 1 && need <= epi->splitk_ws_bytes) {
+      c.ksplit = a.ksplit = nsplit;
+      c.steps_per_split = a.steps_per_split = per;
+      a.slab = static_cast<float*>(epi->splitk_ws);
+      a.col_partial = nullptr;                               // (the partial tiles are not the stored tile)
+      if (epi->col_nblk_out) *epi->col_nblk_out = 0;
+    }
+  }
+}
+
+// The whole decision of a forward-type launch.  `a` holds the problem (ig_args + geometry + classes); on return it is the
+// chosen kernel's argument block.
+FwdChoice choose_fwd(IgArgs& a, bool veca, int bn, int dtype, const TdgEpilogue* epi, const ConvSwitches& sw) {
+#ifdef TDG_STAMPS
+  a.debug = sw.debug_ablate;
+  a.stamps = stamp_ptr();
+#endif
+  int mmax = 0;
+  for (int c = 0; c < a.nclasses; ++c) mmax = a.cls[c].M > mmax ? a.cls[c].M : mmax;
+  FwdChoice c = choose_fwd_tile(a, veca, bn, dtype == TDG_BF16, mmax, sw);
+  c.dtype = dtype;
+  c.veca = veca;
+#ifdef TDG_STAMPS
+  if (c.family == FWD_PATCH && c.bm == 192 && sw.patch_abl >= 1 && sw.patch_abl <= 4) c.abl = sw.patch_abl;
+#endif
+  place_fwd(a, c, mmax, epi, sw);
+  return c;
+}
+
+// A choice to its template instantiation: every forward-type kernel variant is instantiated here and nowhere else.
+template <typename T>
+int launch_fwd(const IgArgs& a, const FwdChoice& c, double flops, hipStream_t s) {
+  if (c.rc) return c.rc;
+  const auto tile = [&](int bm, int bn, int ns = 0, int ws = 0, int pieces = 0) {
+    return c.bm == bm && c.bn == bn && c.ns == ns && c.ws == ws && c.pieces == pieces;
+  };
+  if (c.family == FWD_STAGED) {
+    if (tile(128, 16)) return run_fwd_staged<T, 128, 16, 4, 1>(a, c, flops, s);
+    if (tile(128, 64)) return run_fwd_staged<T, 128, 64, 4, 1>(a, c, flops, s);
+    if (tile(128, 128)) return run_fwd_staged<T, 128, 128, 2, 2>(a, c, flops, s);
+    if (tile(128, 208)) return run_fwd_staged<T, 128, 208, 4, 1>(a, c, flops, s);
+    if (tile(64, 208)) return run_fwd_staged<T, 64, 208, 4, 1>(a, c, flops, s);
+  } else if (c.family == FWD_DMA) {
+    if (tile(64, 112, 3)) return run_fwd_dma<T, 64, 112, 3>(a, c, flops, s);
+    if (tile(128, 112, 3)) return run_fwd_dma<T, 128, 112, 3>(a, c, flops, s);
+    if (tile(256, 112, 3)) return run_fwd_dma<T, 256, 112, 3>(a, c, flops, s);
+    if (tile(128, 64, 3)) return run_fwd_dma<T, 128, 64, 3>(a, c, flops, s);
+    if (tile(128, 128, 3)) return run_fwd_dma<T, 128, 128, 3>(a, c, flops, s);
+    if (tile(256, 128, 3)) return run_fwd_dma<T, 256, 128, 3>(a, c, flops, s);
+    if (tile(128, 208, 3)) return run_fwd_dma<T, 128, 208, 3>(a, c, flops, s);
+    if (tile(192, 208, 2)) return run_fwd_dma<T, 192, 208, 2>(a, c, flops, s);
+    if (tile(192, 208, 3)) return run_fwd_dma<T, 192, 208, 3>(a, c, flops, s);
+    if (tile(256, 208, 2)) return run_fwd_dma<T, 256, 208, 2>(a, c, flops, s);
+    if constexpr (sizeof(T) == 2) {
+      if (tile(128, 208, 3, 1)) return run_fwd_dma<T, 128, 208, 3, 1>(a, c, flops, s);
+      if (tile(192, 208, 3, 1)) return run_fwd_dma<T, 192, 208, 3, 1>(a, c, flops, s);
+    }
+  } else if constexpr (sizeof(T) == 2) {
+    if (c.family == FWD_BP) {
+      if (c.bn == 128) return run_fwd_bp<128>(a, c, flops, s);
+      if (c.bn == 64) return run_fwd_bp<64>(a, c, flops, s);
+    }
+#ifdef TDG_STAMPS
+    // ablation instantiations (their results are garbage): compiled into the diagnostic library (build.sh stamps) only
+    if (c.abl == 1) return run_fwd_patch<192, 208, PT_CK, PT_PIECES, 3, 1>(a, c, flops, s);
+    if (c.abl == 2) return run_fwd_patch<192, 208, PT_CK, PT_PIECES, 3, 2>(a, c, flops, s);
+    if (c.abl == 3) return run_fwd_patch<192, 208, PT_CK, PT_PIECES, 3, 3>(a, c, flops, s);
+    if (c.abl == 4) return run_fwd_patch<192, 208, PT_CK, PT_PIECES, 3, 4>(a, c, flops, s);
+#endif
+    if (tile(192, 208, 3, 1, PT_PIECES)) return run_fwd_patch<192, 208, PT_CK, PT_PIECES, 3>(a, c, flops, s);
+    if (tile(128, 208, 4, 1, 12)) return run_fwd_patch<128, 208, PT_CK, 12, 4>(a, c, flops, s);
+    if (tile(128, 208, 3, 1, 12)) return run_fwd_patch<128, 208, PT_CK, 12, 3>(a, c, flops, s);
+    if (tile(128, 208, 3, 1, PT_PIECES)) return run_fwd_patch<128, 208, PT_CK, PT_PIECES, 3>(a, c, flops, s);
+    if (tile(256, 128, 3, 1, 28)) return run_fwd_patch<256, 128, 4, 28, 3>(a, c, flops, s);
+    if (tile(256, 64, 3, 1, 28)) return run_fwd_patch<256, 64, 4, 28, 3>(a, c, flops, s);
+  }
+  tdg_set_error("igemm_fwd: no kernel for family %d, tile %d x %d", c.family, c.bm, c.bn);
   return TDG_EUNSUPPORTED;
 }
 
 template <typename T, int BKK, int BN, int WGK, int WGN>
-int launch_wgrad_cfg(const WgArgs& a, bool veca, double flops, hipStream_t s) {
+int run_wgrad_staged(const WgArgs& a, bool veca, const char* name, double flops, hipStream_t s) {
   constexpr int MR = WgGeom<T>::MR;
   const size_t lds = (size_t)MR * (WgGeom<T>::pitch(BKK) + WgGeom<T>::pitch(BN)) + IG_MAX_TAPS * sizeof(int);
   const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(256);
-  const char* name = TDG_NAME("igemm_wgrad_kernel<%s,%d,%d>", sizeof(T) == 2 ? "bf16" : "f32", BKK, BN);
   return tdg_launch(name, 0, flops, s, [&] {
     if (veca)
       hipLaunchKernelGGL((igemm_wgrad_kernel<T, BKK, BN, WGK, WGN, true>), grid, block, lds, s, a);
@@ -3786,28 +3912,12 @@ int launch_wgrad_cfg(const WgArgs& a, bool veca, double flops, hipStream_t s) {
 }
 
 template <int BN, int MODE>
-int launch_wgrad_dma(WgArgs& a, double flops, hipStream_t s) {
+int run_wgrad_dma(const WgArgs& a, const char* name, double flops, hipStream_t s) {
   const size_t lds = 4 * (size_t)WD_MR * WD_ROWB + IG_MAX_TAPS * sizeof(int);
   const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(512);
-#ifdef TDG_STAMPS
-  a.stamps = stamp_ptr();
-#endif
-  const char* name = TDG_NAME("igemm_wgrad_dma_kernel<bf16,256,%d,%d>", BN, MODE);
   return tdg_launch<igemm_wgrad_dma_kernel<BN, MODE>>(name, (int)lds, flops, s, [&] {
     hipLaunchKernelGGL((igemm_wgrad_dma_kernel<BN, MODE>), grid, block, lds, s, a);
   });
-}
-
-template <typename T>
-int launch_wgrad(WgArgs& a, bool veca, int bn, double flops, hipStream_t s) {
-  switch (bn) {
-    case 16: return launch_wgrad_cfg<T, 128, 16, 4, 1>(a, veca, flops, s);
-    case 64: return launch_wgrad_cfg<T, 128, 64, 4, 1>(a, veca, flops, s);
-    case 128: return launch_wgrad_cfg<T, 128, 128, 2, 2>(a, veca, flops, s);
-    case 208: return launch_wgrad_cfg<T, 128, 208, 4, 1>(a, veca, flops, s);
-  }
-  tdg_set_error("igemm_wgrad: no tile config for BN=%d", bn);
-  return TDG_EUNSUPPORTED;
 }
 
 inline double conv_flops(const TdgConvDesc* d, int n_images) {
@@ -3847,16 +3957,15 @@ inline int eff_channels(int c, int cs, int vec) {
 // forward-type kernel reads the sliced order through k_decode.  cv: chunks per tap.  Returns cv for the plain order.
 // nrows: the GEMM's columns (rows of the packed operand): the 4-chunk order is for igemm_fwd_patch_kernel's 128- / 64-column
 // tiles only (a one-column problem keeps the plain order conv_n1_fwd_kernel reads).
-inline int k_slice_chunks(int dtype, int cv, int nrows) {
-  static const int enabled = getenv("TDG_KSLICE") ? atoi(getenv("TDG_KSLICE")) : 1;   // diagnostics: 0 = plain order everywhere
-  if (!enabled || dtype != TDG_BF16) return cv;
+inline int k_slice_chunks(int dtype, int cv, int nrows, const ConvSwitches& sw) {
+  if (!sw.kslice || dtype != TDG_BF16) return cv;
   if (cv >= 5 && cv % 5 == 0) return 5;
   // 32-channel slices (pix2pix / VAE widths, 64 ... 1024 channels) for the block-tile form of igemm_fwd_patch_kernel: opt-in
-  // (TDG_BLOCKPATCH=1, read per call: the variant tests set it before they build their convs).  Measured in round 4 on
+  // (ConvSwitches.blockpatch, read per call: the variant tests set it before they build their convs).  Measured in round 4 on
   // pix2pix bs 64: the block-patch kernel takes 5.87 ms where the slab kernel takes 5.34 (and the slab kernel itself loses
   // 4 % on the sliced K order): those layers run 16 - 64 K steps per workgroup and spend as long in prologue + epilogue as in
   // the loop, so less intake per step buys nothing.
-  if (cv >= 8 && cv % 4 == 0 && nrows > 32 && getenv("TDG_BLOCKPATCH") && atoi(getenv("TDG_BLOCKPATCH")) == 1) return 4;
+  if (cv >= 8 && cv % 4 == 0 && nrows > 32 && sw.blockpatch == 1) return 4;
   return cv;
 }
 
@@ -3865,10 +3974,9 @@ inline int k_slice_chunks(int dtype, int cv, int nrows) {
 // class keeps a workgroup's live input at 1/4 of its slab for 4-9 consecutive taps: with 32 workgroups per XCD that
 // fits the 4 MB L2, where the natural row-major order re-fetched every pixel ~3x from beyond L2 (FETCH_SIZE 2.9x the
 // algorithmic bytes of the 192-row kernel).  Stride 1: natural order (all taps share the region anyway).
-inline int fwd_tap_order(const TdgConvDesc* d, int* ord) {
-  static const int enabled = getenv("TDG_TAPORDER") ? atoi(getenv("TDG_TAPORDER")) : 1;   // diagnostics: 0 = row-major
+inline int fwd_tap_order(const TdgConvDesc* d, const ConvSwitches& sw, int* ord) {
   int n = 0;
-  if (d->stride == 2 && enabled) {
+  if (d->stride == 2 && sw.taporder) {
     for (int pa = 0; pa < 2; ++pa)
       for (int pb = 0; pb < 2; ++pb)
         for (int kh = pa; kh < d->kh; kh += 2)
@@ -3922,13 +4030,11 @@ struct Col2imPlan {
   size_t w_bytes, lds;
 };
 
-bool plan_bwd_col2im(const TdgConvDesc* d, const BwdClassPlan* cls, Col2imPlan* f) {
-  static const int enabled = getenv("TDG_COL2IM") ? atoi(getenv("TDG_COL2IM")) : 1;   // diagnostics: 0 = fused-class / per-class kernels
-  if (!enabled || d->dtype != TDG_BF16 || d->stride != 2) return false;
+bool plan_bwd_col2im(const TdgConvDesc* d, const ConvSwitches& sw, const BwdClassPlan* cls, Col2imPlan* f) {
+  if (!sw.col2im || d->dtype != TDG_BF16 || d->stride != 2) return false;
   if (d->kh < 2 || d->kw < 2 || d->kh > 6 || d->kw > 6) return false;
   const int ncol = d->kh * d->kw * d->c;
-  static const int maxcol = getenv("TDG_C2I_MAXCOL") ? atoi(getenv("TDG_C2I_MAXCOL")) : 64;   // diagnostics (<= 80)
-  if (ncol > maxcol || ncol > 80) return false;
+  if (ncol > sw.c2i_maxcol || ncol > 80) return false;
   const int ke = eff_channels(d->k, d->ks, 8);
   if (!ke) return false;
   const int nc = 4;                                          // (stride 2)
@@ -3955,8 +4061,7 @@ bool plan_bwd_col2im(const TdgConvDesc* d, const BwdClassPlan* cls, Col2imPlan* 
   f->p_off = (int)tdg_round_up((long long)f->w_bytes, 256) + 256;       // filter | class tap table (256 bytes) | P
   // measured on pix2pix d8 (128 -> 1, 64 x 256 x 256): 48 KB 0.092 ms, 32 KB 0.081 ms, 16-24 KB 0.085 ms (more workgroups per CU
   // overlap the load / multiply / sum phases, smaller tiles re-read more halo); m1's input gradient (4 column tiles): 48 KB best
-  static const int budget_kb = getenv("TDG_C2I_KB") ? atoi(getenv("TDG_C2I_KB")) : 0;   // diagnostics
-  const size_t budget = (size_t)(budget_kb ? budget_kb : (f->NT == 1 ? 32 : 48)) * 1024;
+  const size_t budget = (size_t)(sw.c2i_kb ? sw.c2i_kb : (f->NT == 1 ? 32 : 48)) * 1024;
   int ta = f->GH < 16 ? f->GH : 16, tw = f->GW < 32 ? f->GW : 32;
   auto need = [&](int a_, int w_) { return (size_t)f->p_off + (size_t)(a_ + nhm - 1) * (w_ + nwm - 1) * f->pitch * 4; };
   while (need(ta, tw) > budget && ta > 4) ta = (ta + 1) / 2;
@@ -3980,9 +4085,8 @@ struct FusedPlan {
   size_t w_bytes, lds;
 };
 
-bool plan_bwd_fused(const TdgConvDesc* d, const BwdClassPlan* cls, FusedPlan* f) {
-  static const int enabled = getenv("TDG_FUSE") ? atoi(getenv("TDG_FUSE")) : 1;   // diagnostics: 0 = one launch-z per class
-  if (!enabled || d->dtype != TDG_BF16 || d->stride != 2 || 4 * d->c > 16) return false;
+bool plan_bwd_fused(const TdgConvDesc* d, const ConvSwitches& sw, const BwdClassPlan* cls, FusedPlan* f) {
+  if (!sw.fuse || d->dtype != TDG_BF16 || d->stride != 2 || 4 * d->c > 16) return false;
   if (d->kh < 2 || d->kw < 2) return false;                  // every class needs a tap
   const int ke = eff_channels(d->k, d->ks, 8);
   if (!ke) return false;
@@ -4043,14 +4147,13 @@ struct ThinPlan {
   size_t w_bytes, lds;
 };
 
-bool plan_fwd_thin(const TdgConvDesc* d, ThinPlan* t) {
-  static const int enabled = getenv("TDG_THIN") ? atoi(getenv("TDG_THIN")) : 1;   // diagnostics: 0 = implicit-GEMM kernels, 2 = only the 208-column form
-  if (!enabled || d->dtype != TDG_BF16 || d->c > 4 || d->cs < 4 || (d->cs & 3) || (d->k & 7) || (d->ks & 7)) return false;
+bool plan_fwd_thin(const TdgConvDesc* d, const ConvSwitches& sw, ThinPlan* t) {
+  if (!sw.thin || d->dtype != TDG_BF16 || d->c > 4 || d->cs < 4 || (d->cs & 3) || (d->k & 7) || (d->ks & 7)) return false;
   if (d->ow > TH_PIX) return false;
   // 208-column tiles for wide outputs; 64-column tiles for 32 .. 128 output channels when the descriptor's batch has >= 64k
   // output pixels (smaller launches stay with the implicit-GEMM kernels: too short for the difference to show)
   if (d->k >= 160) t->NC = 208;
-  else if (enabled != 2 && d->k >= 32 && d->k <= 128 && (long long)d->n * d->oh * d->ow >= 65536) t->NC = 64;
+  else if (sw.thin != 2 && d->k >= 32 && d->k <= 128 && (long long)d->n * d->oh * d->ow >= 65536) t->NC = 64;
   else return false;
   const int tile_rows = t->NC == 208 ? 224 : 64;
   t->Kp = (int)tdg_round_up((long long)d->kh * d->kw * d->c, 32);
@@ -4088,11 +4191,11 @@ struct FwdPlan {
   size_t bytes;           // packed filter
 };
 
-// k_order = false (sizing) leaves the K order out: its per-call TDG_BLOCKPATCH read belongs to the pack and launch calls
-FwdPlan plan_fwd(const TdgConvDesc* d, bool k_order = true) {
+// k_order = false (sizing) leaves the K order out: the per-call ConvSwitches.blockpatch belongs to the pack and launch calls
+FwdPlan plan_fwd(const TdgConvDesc* d, const ConvSwitches& sw, bool k_order = true) {
   FwdPlan p;
   memset(&p, 0, sizeof(p));
-  p.thin = plan_fwd_thin(d, &p.tp);
+  p.thin = plan_fwd_thin(d, sw, &p.tp);
   p.es = tdg_dtype_size(d->dtype);
   p.vec = 16 / p.es;
   p.bke = IG_BKB / p.es;
@@ -4103,8 +4206,8 @@ FwdPlan plan_fwd(const TdgConvDesc* d, bool k_order = true) {
   p.Kp = (int)tdg_round_up((long long)p.ntaps * p.C, p.bke);
   p.bytes = p.thin ? p.tp.w_bytes : (size_t)d->k * p.Kp * p.es;
   if (k_order) {
-    p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->k) : p.C;
-    fwd_tap_order(d, p.ord);
+    p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->k, sw) : p.C;
+    fwd_tap_order(d, sw, p.ord);
   }
   return p;
 }
@@ -4127,7 +4230,7 @@ struct BwdDataPlan {
   size_t bytes;                        // packed filter
 };
 
-BwdDataPlan plan_bwd_data(const TdgConvDesc* d, bool k_order = true) {
+BwdDataPlan plan_bwd_data(const TdgConvDesc* d, const ConvSwitches& sw, bool k_order = true) {
   BwdDataPlan p;
   memset(&p, 0, sizeof(p));
   p.es = tdg_dtype_size(d->dtype);
@@ -4137,10 +4240,10 @@ BwdDataPlan plan_bwd_data(const TdgConvDesc* d, bool k_order = true) {
   p.veca = ke != 0;
   p.C = p.veca ? ke : d->k;
   p.nc = plan_bwd_classes(d, p.cls);
-  if (plan_bwd_col2im(d, p.cls, &p.cp)) {
+  if (plan_bwd_col2im(d, sw, p.cls, &p.cp)) {
     p.form = BWD_COL2IM;
     p.bytes = p.cp.w_bytes;
-  } else if (plan_bwd_fused(d, p.cls, &p.fp)) {
+  } else if (plan_bwd_fused(d, sw, p.cls, &p.fp)) {
     p.form = BWD_FUSED;
     p.bytes = p.fp.w_bytes;
   } else {
@@ -4150,7 +4253,7 @@ BwdDataPlan plan_bwd_data(const TdgConvDesc* d, bool k_order = true) {
       p.off[i] = p.bytes;
       p.bytes += (size_t)d->c * p.Kp[i] * p.es;
     }
-    if (k_order) p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->c) : p.C;
+    if (k_order) p.ck = p.veca ? k_slice_chunks(d->dtype, p.C / p.vec, d->c, sw) : p.C;
   }
   return p;
 }
@@ -4164,7 +4267,7 @@ struct WgradPlan {
   size_t ws_bytes;
 };
 
-WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
+WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images, const ConvSwitches& sw) {
   WgradPlan p;
   const int es = tdg_dtype_size(d->dtype), vec = 16 / es;
   const int mr = d->dtype == TDG_BF16 ? WgGeom<bf16_t>::MR : WgGeom<float>::MR;
@@ -4172,16 +4275,10 @@ WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
   const long long KK = (long long)d->kh * d->kw * (ce ? ce : d->c);
   const int bn = pick_bn(d->k);
   // large bf16 filter gradients take the LDS-DMA kernel (256 x 208 tiles, one workgroup per CU)
-  const char* e = getenv("TDG_WDMA");                   // diagnostics: 0 disables
-  p.dma = false;
-  if (!(e && atoi(e) == 0) && d->dtype == TDG_BF16) {
-    static const int min_kk = getenv("TDG_WDMA_MINKK") ? atoi(getenv("TDG_WDMA_MINKK")) : 128;    // diagnostics
-    p.dma = ce != 0 && (bn == 208 || (bn == 128 && d->k > 112)) && KK >= min_kk;
-  }
+  p.dma = sw.wdma != 0 && d->dtype == TDG_BF16 && ce != 0 && (bn == 208 || (bn == 128 && d->k > 112)) && KK >= sw.wdma_minkk;
   // column tile: pick_bn's, except that the LDS-DMA kernel takes 256-column tiles for N % 256 == 0
   // (pix2pix / VAE widths 256, 512, 1024: a third fewer operand bytes per MAC than 256 x 128)
-  static const int wide = getenv("TDG_WG256") ? atoi(getenv("TDG_WG256")) : 1;     // diagnostics: 0 = 128-column tiles
-  p.bn = wide && bn == 128 && p.dma && d->k % 256 == 0 ? 256 : bn;
+  p.bn = sw.wg256 && bn == 128 && p.dma && d->k % 256 == 0 ? 256 : bn;
   p.ntiles_k = tdg_ceil_div(KK, p.dma ? 256 : 128);
   const int M = n_images * d->oh * d->ow;
   const int tiles = p.ntiles_k * tdg_ceil_div(d->k, p.bn);
@@ -4189,7 +4286,6 @@ WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
   if (p.dma) {
     // one workgroup per CU: the fewest splits (each costs an f32 slab written and re-read) whose last round of
     // 256 workgroups is within 10 % of the best fill any split count up to 16 (few tiles: up to 256 / tiles) reaches
-    static const int force = getenv("TDG_WSPLIT") ? atoi(getenv("TDG_WSPLIT")) : 0;   // diagnostics
     double best = 0.0;
     const int sp_max = tiles >= 16 ? 16 : 256 / tiles;    // few tiles: up to one round of splits
     for (int sp = 1; sp <= sp_max; ++sp) {
@@ -4201,7 +4297,7 @@ WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
       const double fill = (double)tiles * sp / (256.0 * tdg_ceil_div((long long)tiles * sp, 256));
       if (fill >= 0.9 * best) { want = sp; break; }
     }
-    if (force) want = force;
+    if (sw.wsplit) want = sw.wsplit;
   }
   const int max_split = tdg_ceil_div(M, mr * 4);        // keep >= 4 steps per split
   if (want > max_split) want = max_split;
@@ -4214,6 +4310,75 @@ WgradPlan plan_wgrad(const TdgConvDesc* d, int n_images) {
   p.nsplit = tdg_ceil_div(M, p.m_per_split);
   p.ws_bytes = (size_t)p.nsplit * (size_t)tdg_round_up((long long)d->kh * d->kw * d->c * d->k, 4) * sizeof(float);
   return p;
+}
+
+// The kernel variant of one filter-gradient launch, next to its plan: it needs the launch's argument block (two-source
+// switch row, tiles) on top of the descriptor.
+enum { WG_STAGED, WG_DMA, WG_PATCH };   // igemm_wgrad_kernel, igemm_wgrad_dma_kernel, igemm_wgrad_patch_kernel
+struct WgChoice {
+  int family, dtype, bn;
+  bool veca;              // WG_STAGED: 16-byte vector gather
+  int mode;               // WG_DMA: loader mode of the gathered operand (WdLoader)
+  int nw;                 // WG_PATCH: waves per workgroup (8, or 4 = one per SIMD); the pieces per wave are wp.nslot
+  WpPlan wp;              // WG_PATCH
+};
+
+WgChoice choose_wgrad(const TdgConvDesc* d, const WgradPlan& p, const WgArgs& a, bool veca, const ConvSwitches& sw) {
+  WgChoice c;
+  memset(&c, 0, sizeof(c));
+  c.dtype = d->dtype;
+  c.bn = p.bn;
+  c.veca = veca;
+  // loader mode: 1 = a 64-row step of whole images, 2 = a rectangle of one image (whole grid rows, or a 64-column piece of
+  // one), 0 = anything else
+  const int ghw = d->oh * d->ow;
+  if (WD_MR % ghw == 0) c.mode = 1;
+  else if (ghw % WD_MR == 0 && (d->ow % WD_MR == 0 || WD_MR % d->ow == 0) && a.m_switch % WD_MR == 0 &&
+           d->pad_t <= WD_HALO && d->pad_l <= WD_HALO) c.mode = 2;
+  if (sw.wdma_slowa != SW_UNSET) c.mode = 0;
+  // whole-image steps of a 208-column problem: the patch-resident kernel (tdg_wgrad_patch.hip) where its plan applies
+  if (p.dma && p.bn == 208 && c.mode == 1 && sw.wpatch != 0 && tdg_wgrad_patch_plan(a, &c.wp)) {
+    c.family = WG_PATCH;
+    c.nw = tdg_wgrad_patch_waves(&c.wp, sw.wpatch_nw);
+  } else {
+    c.family = p.dma ? WG_DMA : WG_STAGED;
+  }
+  return c;
+}
+
+const char* wgrad_choice_name(const WgChoice& c) {
+  switch (c.family) {
+    case WG_STAGED: return kept_name("igemm_wgrad_kernel<%s,128,%d>", c.dtype == TDG_BF16 ? "bf16" : "f32", c.bn);
+    case WG_DMA: return kept_name("igemm_wgrad_dma_kernel<bf16,256,%d,%d>", c.bn, c.mode);
+    default: return kept_name("igemm_wgrad_patch_kernel<bf16,256,208,%d,%d>", c.nw, c.wp.nslot);
+  }
+}
+
+template <typename T>
+int launch_wgrad_staged(const WgArgs& a, const WgChoice& c, const char* name, double flops, hipStream_t s) {
+  switch (c.bn) {
+    case 16: return run_wgrad_staged<T, 128, 16, 4, 1>(a, c.veca, name, flops, s);
+    case 64: return run_wgrad_staged<T, 128, 64, 4, 1>(a, c.veca, name, flops, s);
+    case 128: return run_wgrad_staged<T, 128, 128, 2, 2>(a, c.veca, name, flops, s);
+    case 208: return run_wgrad_staged<T, 128, 208, 4, 1>(a, c.veca, name, flops, s);
+  }
+  tdg_set_error("igemm_wgrad: no tile config for BN=%d", c.bn);
+  return TDG_EUNSUPPORTED;
+}
+
+int launch_wgrad(WgArgs& a, const WgChoice& c, double flops, hipStream_t s) {
+  const char* name = wgrad_choice_name(c);
+  if (c.family == WG_PATCH) return tdg_wgrad_patch_launch(a, c.wp, c.nw, name, flops, s);
+  if (c.family == WG_STAGED)
+    return c.dtype == TDG_BF16 ? launch_wgrad_staged<bf16_t>(a, c, name, flops, s) : launch_wgrad_staged<float>(a, c, name, flops, s);
+#ifdef TDG_STAMPS
+  a.stamps = stamp_ptr();
+#endif
+  const auto go = [&](auto bn_c) -> int {
+    constexpr int B = decltype(bn_c)::value;
+    return c.mode == 1 ? run_wgrad_dma<B, 1>(a, name, flops, s) : (c.mode == 2 ? run_wgrad_dma<B, 2>(a, name, flops, s) : run_wgrad_dma<B, 0>(a, name, flops, s));
+  };
+  return c.bn == 208 ? go(IntC<208>{}) : c.bn == 256 ? go(IntC<256>{}) : go(IntC<128>{});
 }
 
 // The caller's epilogue into a kernel's argument block, for the fields that block has.  Also *col_nblk_out = 0: every
@@ -4236,7 +4401,7 @@ void set_epilogue(A& f, const TdgEpilogue* e) {
   if (e && e->col_nblk_out) *e->col_nblk_out = 0;
 }
 
-// an implicit-GEMM launch's arguments with the caller's epilogue and no split-K (launch_fwd_dma may split)
+// an implicit-GEMM launch's arguments with the caller's epilogue and no split-K (place_fwd may split)
 IgArgs ig_args(const void* src, const void* wp, void* out, const TdgEpilogue* epi) {
   IgArgs a;
   memset(&a, 0, sizeof(a));
@@ -4249,18 +4414,33 @@ IgArgs ig_args(const void* src, const void* wp, void* out, const TdgEpilogue* ep
   return a;
 }
 
+// Every conv entry point below takes `dry`: non-null is tdg_conv2d_dispatch asking -- the same checks, plan and choice,
+// then the chosen kernel's name (answer) instead of a launch.
+inline int answer(const char** dry, const char* name) {
+  *dry = name;
+  return TDG_OK;
+}
+
+// the end of both forward-type entry points: choose, then launch
+int choose_and_launch_fwd(IgArgs& a, bool veca, int bn, int dtype, double flops, const TdgEpilogue* epi, const ConvSwitches& sw,
+                          hipStream_t s, const char** dry) {
+  const FwdChoice c = choose_fwd(a, veca, bn, dtype, epi, sw);
+  if (dry) return c.rc ? c.rc : answer(dry, fwd_choice_name(c));
+  return dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, c, flops, s) : launch_fwd<float>(a, c, flops, s);
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t tdg_packed_filter_fwd_bytes(const TdgConvDesc* d) {
   if (validate_desc(d, "tdg_packed_filter_fwd_bytes") != TDG_OK) return 0;
-  return plan_fwd(d, false).bytes;
+  return plan_fwd(d, conv_switches(), false).bytes;
 }
 
 size_t tdg_packed_filter_bwd_bytes(const TdgConvDesc* d) {
   if (validate_desc(d, "tdg_packed_filter_bwd_bytes") != TDG_OK) return 0;
-  return plan_bwd_data(d, false).bytes;
+  return plan_bwd_data(d, conv_switches(), false).bytes;
 }
 
 // ---- packing jobs ------------------------------------------------------------------------------------------------
@@ -4363,7 +4543,7 @@ int tdg_pack_filter_fwd(const TdgConvDesc* d, const float* w, void* packed, void
   int rc = validate_desc(d, "tdg_pack_filter_fwd");
   if (rc) return rc;
   TDG_CHECK_ARG(w && packed, "tdg_pack_filter_fwd: null pointer");
-  const FwdPlan p = plan_fwd(d);
+  const FwdPlan p = plan_fwd(d, conv_switches());
   if (p.thin) return launch_pack_thin(d, p.tp, w, packed, (hipStream_t)stream);
   PackArgs a;
   build_pack_fwd(d, p, w, packed, &a);
@@ -4374,7 +4554,7 @@ int tdg_pack_filter_bwd(const TdgConvDesc* d, const float* w, void* packed, void
   int rc = validate_desc(d, "tdg_pack_filter_bwd");
   if (rc) return rc;
   TDG_CHECK_ARG(w && packed, "tdg_pack_filter_bwd: null pointer");
-  const BwdDataPlan p = plan_bwd_data(d);
+  const BwdDataPlan p = plan_bwd_data(d, conv_switches());
   if (p.form == BWD_COL2IM) {
     PackArgs a;
     build_pack_col2im(d, p.cp, w, packed, &a);
@@ -4426,7 +4606,7 @@ int tdg_pack_filters(const TdgPackJob* jobs, int n_jobs, void* stream) {
     TDG_CHECK_ARG(d->dtype == dtype, "tdg_pack_filters: job %d has dtype %d, job 0 has %d", j, d->dtype, dtype);
     TDG_CHECK_ARG(jobs[j].w, "tdg_pack_filters: job %d has no master filter", j);
     if (jobs[j].packed_fwd) {
-      const FwdPlan p = plan_fwd(d);
+      const FwdPlan p = plan_fwd(d, conv_switches());
       if (p.thin) {
         if (m.thin_blocks == 0) {                              // rides in the multi-job launch (the first one of a call)
           fill_pack_thin(d, p.tp, jobs[j].w, jobs[j].packed_fwd, &m.thin);
@@ -4443,7 +4623,7 @@ int tdg_pack_filters(const TdgPackJob* jobs, int n_jobs, void* stream) {
       }
     }
     if (jobs[j].packed_bwd) {
-      const BwdDataPlan p = plan_bwd_data(d);
+      const BwdDataPlan p = plan_bwd_data(d, conv_switches());
       if (p.form == BWD_COL2IM) {
         PackArgs a;
         build_pack_col2im(d, p.cp, jobs[j].w, jobs[j].packed_bwd, &a);
@@ -4470,19 +4650,21 @@ int tdg_pack_filters(const TdgPackJob* jobs, int n_jobs, void* stream) {
   return flush();
 }
 
-int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void* wp, void* y,
-                   const TdgEpilogue* epi, void* stream) {
+static int conv_fwd(const TdgConvDesc* d, int n_images, const void* x, const void* wp, void* y, const TdgEpilogue* epi,
+                    hipStream_t s, const char** dry) {
   int rc = validate_desc(d, "tdg_conv2d_fwd");
   if (rc) return rc;
   TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_fwd: n_images %d outside (0, %d]", n_images, d->n);
   TDG_CHECK_ARG(x && wp && y, "tdg_conv2d_fwd: null pointer");
   TDG_CHECK_ARG(!epi || epi->mask_mode == TDG_MASK_NONE || epi->mask_src, "tdg_conv2d_fwd: mask without mask_src");
-  const FwdPlan p = plan_fwd(d);
+  const ConvSwitches sw = conv_switches();
+  const FwdPlan p = plan_fwd(d, sw);
   TDG_CHECK_ARG(!p.veca || ((uintptr_t)x & 15) == 0, "tdg_conv2d_fwd: x must be 16-byte aligned (channel stride allows the vector gather)");
-  const hipStream_t s = (hipStream_t)stream;
   const double flops = conv_flops(d, n_images);
   if (p.thin) {                                              // (the filter is packed in thin_fwd_kernel's layout: no other kernel can read it)
     const ThinPlan& tp = p.tp;
+    const char* name = tp.NC == 208 ? "thin_fwd_kernel<bf16>" : "thin_fwd_kernel<bf16,64>";
+    if (dry) return answer(dry, name);
     ThinFwdArgs f;
     memset(&f, 0, sizeof(f));
     f.x = static_cast<const bf16_t*>(x);
@@ -4498,21 +4680,22 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
     f.fd_ow = make_fastdiv(d->ow);
     f.fd_c = make_fastdiv(d->c);
 #ifdef TDG_STAMPS
-    f.debug = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;     // (garbage results: diagnostic library only)
+    f.debug = sw.debug_ablate;
     f.stamps = stamp_ptr();
 #endif
     const dim3 grid(n_images * tp.tiles_per_image * tp.ntiles_n);
     if (tp.NC == 208)
-      return tdg_launch<thin_fwd_kernel<208>>("thin_fwd_kernel<bf16>", 80 * 1024, flops, s, [&] {
+      return tdg_launch<thin_fwd_kernel<208>>(name, 80 * 1024, flops, s, [&] {
         hipLaunchKernelGGL(thin_fwd_kernel<208>, grid, dim3(256), tp.lds, s, f);
       });
-    return tdg_launch<thin_fwd_kernel<64>>("thin_fwd_kernel<bf16,64>", 80 * 1024, flops, s, [&] {
+    return tdg_launch<thin_fwd_kernel<64>>(name, 80 * 1024, flops, s, [&] {
       hipLaunchKernelGGL(thin_fwd_kernel<64>, grid, dim3(256), tp.lds, s, f);
     });
   }
-  static const int n1_enabled = getenv("TDG_CONVN1") ? atoi(getenv("TDG_CONVN1")) : 1;   // diagnostics: 0 = the 128 x 16 MFMA tile
-  if (n1_enabled && d->k == 1 && p.veca && p.ck == p.C / p.vec && p.ntaps <= IG_MAX_TAPS && (long long)n_images * d->oh * d->ow >= 1024 &&
+  if (sw.convn1 && d->k == 1 && p.veca && p.ck == p.C / p.vec && p.ntaps <= IG_MAX_TAPS && (long long)n_images * d->oh * d->ow >= 1024 &&
       !(epi && (epi->accumulate || epi->mask_mode != TDG_MASK_NONE))) {
+    const char* name = d->dtype == TDG_BF16 ? "conv_n1_fwd_kernel<bf16>" : "conv_n1_fwd_kernel<f32>";
+    if (dry) return answer(dry, name);
     ConvN1Args f;                                              // (no column partials from this kernel: the host runs its own pass)
     memset(&f, 0, sizeof(f));
     f.x = x; f.w = wp; f.y = y;
@@ -4527,10 +4710,10 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
     f.fd_ow = make_fastdiv(d->ow);
     const dim3 grid(tdg_ceil_div(f.M, 4));
     if (d->dtype == TDG_BF16)
-      return tdg_launch("conv_n1_fwd_kernel<bf16>", 0, flops, s, [&] {
+      return tdg_launch(name, 0, flops, s, [&] {
         hipLaunchKernelGGL(conv_n1_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, f);
       });
-    return tdg_launch("conv_n1_fwd_kernel<f32>", 0, flops, s, [&] {
+    return tdg_launch(name, 0, flops, s, [&] {
       hipLaunchKernelGGL(conv_n1_fwd_kernel<float>, grid, dim3(256), 0, s, f);
     });
   }
@@ -4559,22 +4742,27 @@ int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void
   c.nh = d->kh; c.nw = d->kw; c.dh0 = -d->pad_t; c.dw0 = -d->pad_l; c.sh = c.sw = 1;
   c.fd_nw = make_fastdiv(c.nw);
   c.fd_nt = make_fastdiv(c.ntaps);
-  const int bn = pick_bn(d->k);
-  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, p.veca, bn, flops, epi, s) : launch_fwd<float>(a, p.veca, bn, flops, epi, s);
+  return choose_and_launch_fwd(a, p.veca, pick_bn(d->k), d->dtype, flops, epi, sw, s, dry);
 }
 
-int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const void* wp, void* x,
-                        const TdgEpilogue* epi, void* stream) {
+int tdg_conv2d_fwd(const TdgConvDesc* d, int n_images, const void* x, const void* wp, void* y,
+                   const TdgEpilogue* epi, void* stream) {
+  return conv_fwd(d, n_images, x, wp, y, epi, (hipStream_t)stream, nullptr);
+}
+
+static int conv_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const void* wp, void* x, const TdgEpilogue* epi,
+                         hipStream_t s, const char** dry) {
   int rc = validate_desc(d, "tdg_conv2d_bwd_data");
   if (rc) return rc;
   TDG_CHECK_ARG(n_images > 0 && n_images <= d->n, "tdg_conv2d_bwd_data: n_images %d outside (0, %d]", n_images, d->n);
   TDG_CHECK_ARG(x && wp && y, "tdg_conv2d_bwd_data: null pointer");
   TDG_CHECK_ARG(!epi || epi->mask_mode == TDG_MASK_NONE || epi->mask_src, "tdg_conv2d_bwd_data: mask without mask_src");
-  const BwdDataPlan p = plan_bwd_data(d);
+  const ConvSwitches sw = conv_switches();
+  const BwdDataPlan p = plan_bwd_data(d, sw);
   TDG_CHECK_ARG(!p.veca || ((uintptr_t)y & 15) == 0, "tdg_conv2d_bwd_data: y must be 16-byte aligned (channel stride allows the vector gather)");
-  const hipStream_t s = (hipStream_t)stream;
   const double flops = conv_flops(d, n_images);
   if (p.form == BWD_COL2IM) {
+    if (dry) return answer(dry, "bwd_col2im_kernel<bf16>");
     const Col2imPlan& cp = p.cp;
     Col2imArgs f;
     memset(&f, 0, sizeof(f));
@@ -4588,7 +4776,7 @@ int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const
     f.TA = cp.TA; f.TW = cp.TW; f.ntr = cp.ntr; f.ntc = cp.ntc; f.HR = cp.HR; f.HC = cp.HC; f.dh_min = cp.dh_min; f.dw_min = cp.dw_min;
     f.p_off = cp.p_off;
 #ifdef TDG_STAMPS
-    f.debug = getenv("TDG_DEBUG_ABLATE") ? atoi(getenv("TDG_DEBUG_ABLATE")) : 0;     // (garbage results: diagnostic library only)
+    f.debug = sw.debug_ablate;
 #endif
     for (int i = 0; i < 4; ++i) {
       const BwdClassPlan& c = p.cls[i];
@@ -4611,6 +4799,7 @@ int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const
     });
   }
   if (p.form == BWD_FUSED) {
+    if (dry) return answer(dry, "bwd_fused_kernel<bf16>");
     const FusedPlan& fp = p.fp;
     FusedBwdArgs f;
     memset(&f, 0, sizeof(f));
@@ -4665,13 +4854,17 @@ int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const
     c.fd_nw = make_fastdiv(c.nw);
     c.fd_nt = make_fastdiv(c.ntaps);
   }
-  const int bn = pick_bn(d->c);
-  return d->dtype == TDG_BF16 ? launch_fwd<bf16_t>(a, p.veca, bn, flops, epi, s) : launch_fwd<float>(a, p.veca, bn, flops, epi, s);
+  return choose_and_launch_fwd(a, p.veca, pick_bn(d->c), d->dtype, flops, epi, sw, s, dry);
+}
+
+int tdg_conv2d_bwd_data(const TdgConvDesc* d, int n_images, const void* y, const void* wp, void* x,
+                        const TdgEpilogue* epi, void* stream) {
+  return conv_bwd_data(d, n_images, y, wp, x, epi, (hipStream_t)stream, nullptr);
 }
 
 size_t tdg_conv2d_bwd_filter_workspace_bytes(const TdgConvDesc* d, int n_images) {
   if (validate_desc(d, "tdg_conv2d_bwd_filter_workspace_bytes") != TDG_OK) return 0;
-  return plan_wgrad(d, n_images).ws_bytes;
+  return plan_wgrad(d, n_images, conv_switches()).ws_bytes;
 }
 
 static int validate_wgrad(const TdgConvDesc* d, int n_images) {
@@ -4681,35 +4874,36 @@ static int validate_wgrad(const TdgConvDesc* d, int n_images) {
   return TDG_OK;
 }
 
-static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_images, const void* x, int n_first, const void* x2,
-                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream);
+static int bwd_filter_impl(const TdgConvDesc* d, const ConvSwitches& sw, int n_images, const void* x, int n_first, const void* x2,
+                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, hipStream_t s, const char** dry);
 
-int tdg_conv2d_bwd_filter(const TdgConvDesc* d, int n_images, const void* x, const void* y, float* dw,
-                          float beta, void* workspace, size_t workspace_bytes, void* stream) {
+static int conv_bwd_filter(const TdgConvDesc* d, int n_images, const void* x, const void* y, float* dw, float beta, void* workspace,
+                           size_t workspace_bytes, hipStream_t s, const char** dry) {
   const int rc = validate_wgrad(d, n_images);
   if (rc) return rc;
-  return bwd_filter_impl(d, plan_wgrad(d, n_images), n_images, x, n_images, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
+  return bwd_filter_impl(d, conv_switches(), n_images, x, n_images, nullptr, y, dw, beta, workspace, workspace_bytes, s, dry);
 }
 
-int tdg_conv2d_bwd_filter2(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
-                           float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
+static int conv_bwd_filter2(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y, float* dw,
+                            float beta, void* workspace, size_t workspace_bytes, hipStream_t s, const char** dry) {
   TDG_CHECK_ARG(n_first > 0 && n_first < n_images && x2, "tdg_conv2d_bwd_filter2: n_first %d outside (0, %d) or null x2", n_first, n_images);
   int rc = validate_wgrad(d, n_images);
   if (rc) return rc;
+  const ConvSwitches sw = conv_switches();
   // one launch when the LDS-DMA kernel applies and the switch row is even (a 2-row DMA instruction never straddles it)
-  const WgradPlan p = plan_wgrad(d, n_images);
-  if (p.dma && ((long long)n_first * d->oh * d->ow) % 2 == 0)
-    return bwd_filter_impl(d, p, n_images, x, n_first, x2, y, dw, beta, workspace, workspace_bytes, stream);
-  rc = bwd_filter_impl(d, plan_wgrad(d, n_first), n_first, x, n_first, nullptr, y, dw, beta, workspace, workspace_bytes, stream);
+  if (plan_wgrad(d, n_images, sw).dma && ((long long)n_first * d->oh * d->ow) % 2 == 0)
+    return bwd_filter_impl(d, sw, n_images, x, n_first, x2, y, dw, beta, workspace, workspace_bytes, s, dry);
+  rc = bwd_filter_impl(d, sw, n_first, x, n_first, nullptr, y, dw, beta, workspace, workspace_bytes, s, dry);
   if (rc) return rc;
   const char* y2 = static_cast<const char*>(y) + (size_t)n_first * d->oh * d->ow * d->ks * tdg_dtype_size(d->dtype);
   const int n2 = n_images - n_first;
-  return bwd_filter_impl(d, plan_wgrad(d, n2), n2, x2, n2, nullptr, y2, dw, 1.0f, workspace, workspace_bytes, stream);
+  return bwd_filter_impl(d, sw, n2, x2, n2, nullptr, y2, dw, 1.0f, workspace, workspace_bytes, s, dry);
 }
 
-// (d and n_images are validated; p = plan_wgrad(d, n_images))
-static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_images, const void* x, int n_first, const void* x2,
-                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
+// One filter-gradient GEMM plus its slab reduction: fills WgArgs, chooses, launches.  (d and n_images are validated.)
+static int bwd_filter_impl(const TdgConvDesc* d, const ConvSwitches& sw, int n_images, const void* x, int n_first, const void* x2,
+                           const void* y, float* dw, float beta, void* workspace, size_t workspace_bytes, hipStream_t s, const char** dry) {
+  const WgradPlan p = plan_wgrad(d, n_images, sw);
   TDG_CHECK_ARG(x && y && dw && workspace, "tdg_conv2d_bwd_filter: null pointer");
   if (workspace_bytes < p.ws_bytes) {
     tdg_set_error("tdg_conv2d_bwd_filter: workspace %zu < %zu bytes", workspace_bytes, p.ws_bytes);
@@ -4751,35 +4945,9 @@ static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_image
   a.ntiles_k = p.ntiles_k;
   for (int kh = 0; kh < d->kh; ++kh)
     for (int kw = 0; kw < d->kw; ++kw) a.tap[kh * d->kw + kw] = pack_tap(kh - d->pad_t, kw - d->pad_l);
-  const hipStream_t s = (hipStream_t)stream;
-  const double flops = conv_flops(d, n_images);
-  // loader mode of the gathered operand (WdLoader): 1 = a 64-row step of whole images, 2 = a rectangle of one image
-  // (whole grid rows, or a 64-column piece of one), 0 = anything else.  TDG_WDMA_SLOWA (diagnostics) forces 0.
-  const int ghw = d->oh * d->ow;
-  int mode = 0;
-  if (WD_MR % ghw == 0) mode = 1;
-  else if (ghw % WD_MR == 0 && (d->ow % WD_MR == 0 || WD_MR % d->ow == 0) && a.m_switch % WD_MR == 0 &&
-           d->pad_t <= WD_HALO && d->pad_l <= WD_HALO) mode = 2;
-  if (getenv("TDG_WDMA_SLOWA")) mode = 0;
-  auto go = [&](auto bn_c) -> int {
-    constexpr int B = decltype(bn_c)::value;
-    return mode == 1 ? launch_wgrad_dma<B, 1>(a, flops, s) : (mode == 2 ? launch_wgrad_dma<B, 2>(a, flops, s) : launch_wgrad_dma<B, 0>(a, flops, s));
-  };
-  // whole-image steps of a 208-column problem: the patch-resident kernel (tdg_wgrad_patch.hip) where its plan applies.
-  // TDG_WPATCH=0 (variant tests) keeps the slab kernel.
-  int rc = TDG_OK;
-  bool patched = false;
-  if (p.dma && p.bn == 208 && mode == 1 && !(getenv("TDG_WPATCH") && atoi(getenv("TDG_WPATCH")) == 0)) {
-    WpPlan wp;
-    if (tdg_wgrad_patch_plan(a, &wp)) {
-      rc = tdg_wgrad_patch_launch(a, wp, flops, s);
-      if (rc) return rc;
-      patched = true;
-    }
-  }
-  if (!patched)
-    rc = p.dma ? (p.bn == 208 ? go(IntC<208>{}) : p.bn == 256 ? go(IntC<256>{}) : go(IntC<128>{}))
-               : d->dtype == TDG_BF16 ? launch_wgrad<bf16_t>(a, veca, p.bn, flops, s) : launch_wgrad<float>(a, veca, p.bn, flops, s);
+  const WgChoice c = choose_wgrad(d, p, a, veca, sw);
+  if (dry) return answer(dry, wgrad_choice_name(c));
+  const int rc = launch_wgrad(a, c, conv_flops(d, n_images), s);
   if (rc) return rc;
   const size_t n = (size_t)a.ntaps * d->c * d->k;
   return tdg_launch("slab_reduce", 0, 0.0, s, [&] {
@@ -4791,6 +4959,42 @@ static int bwd_filter_impl(const TdgConvDesc* d, const WgradPlan& p, int n_image
       hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slabs, dw, n, a.nsplit, (size_t)a.slab_stride, beta);
     }
   }, false);                                                   // (tdg_last_kernel keeps the GEMM's name)
+}
+
+int tdg_conv2d_bwd_filter(const TdgConvDesc* d, int n_images, const void* x, const void* y, float* dw,
+                          float beta, void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_bwd_filter(d, n_images, x, y, dw, beta, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+int tdg_conv2d_bwd_filter2(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
+                           float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_bwd_filter2(d, n_images, x, n_first, x2, y, dw, beta, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+int tdg_conv2d_dispatch(const TdgConvDesc* d, int n_images, int form, const TdgEpilogue* epi, int n_first, char* name, size_t name_bytes) {
+  TDG_CHECK_ARG(name && name_bytes > 0, "tdg_conv2d_dispatch: no name buffer");
+  name[0] = 0;
+  // stands for every tensor, filter and workspace pointer: non-null, aligned, never dereferenced
+  void* const p = reinterpret_cast<void*>((uintptr_t)4096);
+  TdgEpilogue e;
+  int nblk = 0;
+  if (epi) {
+    e = *epi;
+    if (e.col_nblk_out) e.col_nblk_out = &nblk;              // (the real call's only write through the epilogue)
+  }
+  const char* kernel = nullptr;
+  int rc;
+  switch (form) {
+    case TDG_FORM_FWD: rc = conv_fwd(d, n_images, p, p, p, epi ? &e : nullptr, nullptr, &kernel); break;
+    case TDG_FORM_BWD_DATA: rc = conv_bwd_data(d, n_images, p, p, p, epi ? &e : nullptr, nullptr, &kernel); break;
+    case TDG_FORM_BWD_FILTER:
+      rc = n_first ? conv_bwd_filter2(d, n_images, p, n_first, p, p, static_cast<float*>(p), 0.f, p, (size_t)-1, nullptr, &kernel)
+                   : conv_bwd_filter(d, n_images, p, p, static_cast<float*>(p), 0.f, p, (size_t)-1, nullptr, &kernel);
+      break;
+    default: TDG_CHECK_ARG(false, "tdg_conv2d_dispatch: bad form %d", form);
+  }
+  if (rc == TDG_OK) snprintf(name, name_bytes, "%s", kernel);
+  return rc;
 }
 
 }  // extern "C"

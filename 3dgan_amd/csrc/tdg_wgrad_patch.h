@@ -1,4 +1,4 @@
-// Patch-resident filter-gradient GEMM (tdg_wgrad_patch.hip): plan + launch, called from bwd_filter_impl (tdg_igemm.hip).
+// Patch-resident filter-gradient GEMM (tdg_wgrad_patch.hip): plan + launch, called from choose_wgrad / launch_wgrad (tdg_igemm.hip).
 #pragma once
 #include "tdg_igemm.h"
 
@@ -17,4 +17,7 @@ struct WpPlan {
   FastDiv fd_nt, fd_rp, fd_nsl;
 };
 bool tdg_wgrad_patch_plan(const WgArgs& a, WpPlan* p);
-int tdg_wgrad_patch_launch(WgArgs& a, WpPlan& p, double flops, hipStream_t s);
+// The wave layout of a plan that holds: nw = 8 waves, or 4 = one per SIMD (ConvSwitches.wpatch_nw in tdg_igemm.hip).  Sets
+// p->nslot and returns the waves; `name` of the launch is formatted from the two by wgrad_choice_name.
+int tdg_wgrad_patch_waves(WpPlan* p, int nw);
+int tdg_wgrad_patch_launch(const WgArgs& a, const WpPlan& p, int nw, const char* name, double flops, hipStream_t s);

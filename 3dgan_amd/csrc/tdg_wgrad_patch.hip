@@ -486,27 +486,26 @@ static bool wp_plan_search(const WgArgs& a, WpPlan* p) {
   return true;
 }
 
+int tdg_wgrad_patch_waves(WpPlan* p, int nw) {
+  const int pieces = WP_GPIECES + p->npa;
+  if (nw == 4) {                                         // one wave per SIMD (512-register waves)
+    p->nslot = tdg_ceil_div(pieces, 4) <= 10 ? 10 : 11;
+    return 4;
+  }
+  p->nslot = tdg_ceil_div(pieces, 8) <= 5 ? 5 : 6;
+  return 8;
+}
+
 template <int NW, int NSLOT>
-static int wp_launch(WgArgs& a, WpPlan& p, double flops, hipStream_t s) {
+static int wp_launch(const WgArgs& a, const WpPlan& p, const char* name, double flops, hipStream_t s) {
   const size_t lds = WP_LDS + IG_MAX_TAPS * sizeof(int);
-  p.nslot = NSLOT;
   const dim3 grid(a.ntiles_k * a.ntiles_n, 1, a.nsplit), block(64 * NW);
-  const char* name = TDG_NAME("igemm_wgrad_patch_kernel<bf16,256,208,%d,%d>", NW, NSLOT);
   return tdg_launch<igemm_wgrad_patch_kernel<NW, NSLOT>>(name, (int)lds, flops, s, [&] {
     hipLaunchKernelGGL((igemm_wgrad_patch_kernel<NW, NSLOT>), grid, block, lds, s, a, p);
   });
 }
 
-int tdg_wgrad_patch_launch(WgArgs& a, WpPlan& p, double flops, hipStream_t s) {
-  const char* e = getenv("TDG_WPATCH_NW");               // variant tests: 4 = one wave per SIMD (512-register waves)
-  const int nw = e ? atoi(e) : 8;
-  const int pieces = WP_GPIECES + p.npa;
-  if (nw == 4) {
-    const int ns = tdg_ceil_div(pieces, 4);
-    if (ns <= 10) return wp_launch<4, 10>(a, p, flops, s);
-    return wp_launch<4, 11>(a, p, flops, s);
-  }
-  const int ns = tdg_ceil_div(pieces, 8);
-  if (ns <= 5) return wp_launch<8, 5>(a, p, flops, s);
-  return wp_launch<8, 6>(a, p, flops, s);
+int tdg_wgrad_patch_launch(const WgArgs& a, const WpPlan& p, int nw, const char* name, double flops, hipStream_t s) {
+  if (nw == 4) return p.nslot == 10 ? wp_launch<4, 10>(a, p, name, flops, s) : wp_launch<4, 11>(a, p, name, flops, s);
+  return p.nslot == 5 ? wp_launch<8, 5>(a, p, name, flops, s) : wp_launch<8, 6>(a, p, name, flops, s);
 }

@@ -157,6 +157,14 @@ int tdg_conv2d_bwd_filter(const TdgConvDesc* d, int n_images, const void* x, con
  * (tangents of the penalty's double backward, models/gan.py:228) against one delta tensor. */
 int tdg_conv2d_bwd_filter2(const TdgConvDesc* d, int n_images, const void* x, int n_first, const void* x2, const void* y,
                            float* dw, float beta, void* workspace, size_t workspace_bytes, void* stream);
+/* Host-only query: the kernel variant a conv launch would take.  Runs the validation, plan and choice of the entry point
+ * that `form` names and writes into `name` what tdg_last_kernel() would return after that call; nothing is enqueued.
+ * Of `epi` only the scalar fields, the sizes and whether each pointer is NULL are read.  n_first: TDG_FORM_BWD_FILTER only --
+ * 0 asks about tdg_conv2d_bwd_filter, anything else about tdg_conv2d_bwd_filter2 with that n_first.  Returns the status
+ * the call's argument checks would return, assuming non-NULL, 16-byte aligned buffers and a large enough workspace. */
+enum { TDG_FORM_FWD = 0, TDG_FORM_BWD_DATA = 1, TDG_FORM_BWD_FILTER = 2 };
+int tdg_conv2d_dispatch(const TdgConvDesc* d, int n_images, int form, const TdgEpilogue* epi, int n_first, char* name,
+                        size_t name_bytes);
 
 /* ---- dense fc2-style row ops (tf.matmul with one output unit, ops/layers.py:57 via
  *      models/gan.py:285, and its autodiff) --------------------------------------------- */

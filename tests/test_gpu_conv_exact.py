@@ -3,7 +3,8 @@
 No tolerance is defined here: every comparison is np.array_equal.  The only conditions are the two magnitude caps of
 _exact_conv.check_caps (|v| <= 256 for bf16-stored values, |v| < 2**24 for f32 ones), asserted on the oracle.  The case
 lists are those of tests/test_gpu_kernels.py, imported, so the two files cannot drift.  Each launch prints the kernel
-symbol it dispatched to (`kernel: <form> <symbol>`; run with -s to collect them).
+symbol it dispatched to (`kernel: <form> <symbol>`; run with -s to collect them), and that symbol must be the one
+tdg_conv2d_dispatch named when it was asked, just before the launch, with the same arguments.
 """
 import itertools
 
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 from conftest import pkg
+import _conv_dispatch as D
 import _exact_conv as X
 import test_gpu_kernels as G
 
@@ -51,9 +53,42 @@ def last_kernel():
     return pkg('_lib').load().tdg_last_kernel().decode()
 
 
+_ASKED = []                 # what tdg_conv2d_dispatch answered just before the most recent launch of a conv from make()
+
+
+def asking(conv):
+    """Wrap the four launches of `conv`: each first asks the host-only query about the very call it is going to make."""
+    fwd, bwd_data, bwd_filter, bwd_filter2 = conv.fwd, conv.bwd_data, conv.bwd_filter, conv.bwd_filter2
+
+    def ask(n_images, form, epi=None, n_first=0):
+        _ASKED[:] = [D.ask(conv.desc, n_images, form, epi, n_first)]
+
+    def fwd_(x_ptr, y_ptr, n_images, epi=None):
+        epi = conv._with_splitk(epi)
+        ask(n_images, 'fwd', epi)
+        fwd(x_ptr, y_ptr, n_images, epi)
+
+    def bwd_data_(y_ptr, x_ptr, n_images, epi=None):
+        epi = conv._with_splitk(epi)
+        ask(n_images, 'bwd_data', epi)
+        bwd_data(y_ptr, x_ptr, n_images, epi)
+
+    def bwd_filter_(x_ptr, y_ptr, dw, n_images, beta=0.0):
+        ask(n_images, 'bwd_filter')
+        bwd_filter(x_ptr, y_ptr, dw, n_images, beta=beta)
+
+    def bwd_filter2_(x_ptr, n_first, x2_ptr, y_ptr, dw, n_images, beta=0.0):
+        ask(n_images, 'bwd_filter', n_first=n_first)
+        bwd_filter2(x_ptr, n_first, x2_ptr, y_ptr, dw, n_images, beta=beta)
+    conv.fwd, conv.bwd_data, conv.bwd_filter, conv.bwd_filter2 = fwd_, bwd_data_, bwd_filter_, bwd_filter2_
+    return conv
+
+
 def note(form, case):
     kern = last_kernel()
     print('kernel: %s %s %s' % (form, kern, case))
+    assert _ASKED == [kern], '%s of %s: tdg_conv2d_dispatch named %r, the launch took %r' % (form, case, _ASKED, kern)
+    _ASKED.clear()
     return kern
 
 
@@ -76,7 +111,7 @@ def make(K, case, dtype, padding='SAME'):
     dev = torch.device('cuda:0')
     oh, ow, pt, pl = X.geometry(case, padding)
     big, small = K.Act(n, h, w, cin, dtype, dev), K.Act(n, oh, ow, cout, dtype, dev)
-    return big, small, K.Conv(big, small, k, k, s, pt, pl), dev
+    return big, small, asking(K.Conv(big, small, k, k, s, pt, pl)), dev
 
 
 def dev_f32(a, dev):
