@@ -116,6 +116,13 @@ SIGNATURES = {
     'tdg_xsamp_prep': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     'tdg_xsamp_head_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     'tdg_xsamp_head_bwd': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_isamp_prep': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    'tdg_isamp_head_bn_workspace_bytes': (_sz, [_i, _i]),
+    'tdg_isamp_head_bn_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    'tdg_isamp_head_bn_bwd': (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_isamp_rmse_grad': (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    'tdg_isamp_zero_fraction_workspace_bytes': (_sz, []),
+    'tdg_isamp_zero_fraction': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

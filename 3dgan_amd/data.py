@@ -94,6 +94,33 @@ class SyntheticEstimatorSource:
         return self.x[k], self.y[k], self.x_loc, self.y_loc, self.x_full[k], self.y_full[k]
 
 
+class SyntheticSamplerSource:
+    """The tuple `--model improved_sampler` reads, by its number of entries: 2 = (x [B,S,S,3], y [B,S,S,1]), 4 = the pair and
+    the location ramps x_loc, y_loc [B,S,S,1] of an S x S frame cut whole (nyuv2 `--include_location`), 5 = those and mean_vec
+    [B,S,S,1], every pixel the mean of that image's y (nyuv2 `--normalize`).  x ~ U[0,1); y has a level of its own per image,
+    U(0.1, 0.9), plus U(-0.02, 0.02) noise, as SyntheticEstimatorSource's."""
+
+    def __init__(self, n_batches, batch_size, device, size=64, entries=5, seed=1234, rank=0):
+        if entries not in (2, 4, 5):
+            raise ValueError('SyntheticSamplerSource serves 2, 4 or 5 entries, not %r' % (entries,))
+        g = torch.Generator(device='cpu').manual_seed(seed + 7919 * rank)
+        n, B = n_batches, batch_size
+        level = torch.rand(n, B, 1, 1, 1, generator=g) * 0.8 + 0.1
+        y = level + (torch.rand(n, B, size, size, 1, generator=g) - 0.5) * 0.04
+        ramp = (torch.arange(size, dtype=torch.float64) / (size - 1)).float()
+        self.x = torch.rand(n, B, size, size, 3, generator=g).to(device)
+        self.y = y.to(device)
+        self.x_loc = ramp[None, None, :, None].expand(B, size, size, 1).contiguous().to(device)
+        self.y_loc = ramp[None, :, None, None].expand(B, size, size, 1).contiguous().to(device)
+        self.mean_vec = y.mean(dim=(2, 3, 4), keepdim=True).expand(n, B, size, size, 1).contiguous().to(device)
+        self.entries, self.i = entries, 0
+
+    def next_batch(self):
+        k = self.i % self.x.shape[0]
+        self.i += 1
+        return (self.x[k], self.y[k], self.x_loc, self.y_loc, self.mean_vec[k])[:self.entries]
+
+
 class StreamingSource:
     """The reference's host pipeline for a dataset that stays in HOST memory (data.py:54-58, train.py:171-174):
     cache -> repeat() -> shuffle(buffer_size) -> batch(batch_size * n_gpus), each tower taking its rows of the batch

@@ -65,9 +65,22 @@ def every_model_plugin():
 
 
 def known_model_plugins():
-    """every_model_plugin() and the experimental directory: what `--model` accepts."""
+    """every_model_plugin() and the experimental directory (pinned; `--model` accepts accepted_model_plugins())."""
     found = every_model_plugin()
     found.update(experimental_model_plugins())
+    return found
+
+
+def improved_model_plugins():
+    """The depth sampler family A1-A3, B2, D1, E1 (hem/models/improved_sampler.py): `3dgan_amd/models/improved/`.  It stays out
+    of known_model_plugins(), whose result is pinned like the other two unions'; accepted_model_plugins() adds it."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'improved'), '3dgan_amd.models.improved', 'ModelPlugin')
+
+
+def accepted_model_plugins():
+    """known_model_plugins() and the improved directory: what `--model` accepts."""
+    found = known_model_plugins()
+    found.update(improved_model_plugins())
     return found
 
 
@@ -85,7 +98,7 @@ def data_plugins():
 
 def get_model(name):
     """hem/models/ModelPlugin.py:4-8: the plugin class registered under `name` (KeyError for an unknown name, as there)."""
-    return known_model_plugins()[name]
+    return accepted_model_plugins()[name]
 
 
 def get_dataset(name):

@@ -422,6 +422,51 @@ int tdg_xsamp_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int c
 int tdg_xsamp_head_bwd(int dtype, const void* dfake, int fake_cs, const float* g, const void* cat, int n, int hw, int cin, int cs,
                        const float* w, int mask_mode, float leak, void* dcat, float* dw, float* db, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* ---- improved_sampler (hem/models/improved_sampler.py; 3dgan_amd/csrc/tdg_isamp.hip) ------------------------------------------
+ * tdg_isamp_prep: tdg_xsamp_prep made general (:109-181).  planes P in {3, 5, 6}: [fl(2 x - 1) (3)], + [x_loc | y_loc], + a
+ *   per-pixel mean_vec plane f32 [n,S,S] (x_loc / y_loc may be null for P = 3, mean_vec for P < 6).  Source side S, crop side T at
+ *   offset off (off + T <= S); the row maps x_rows, y_rows as in tdg_xsamp_prep, an entry outside [0, n) clamped into it before it
+ *   becomes an address.  Channels 0..P-1 go to g_in (channel stride g_cs >= P + 1) AND to rgb_in (rgb_cs >= P), each nullable;
+ *   channel P of g_in (the noise) and every padding channel are NOT written.  The depth target fl(2 y[q, off + i, off + j] - 1)
+ *   goes to channel 0 of depth_real [n,T,T,depth_cs] (nullable) and to target f32 [n,T,T] (nullable); without y neither may be
+ *   given.  For P = 6 and mean_vec[b,:,:] == m[b] every written bit is tdg_xsamp_prep's. */
+int tdg_isamp_prep(int dtype, const float* x, const float* x_loc, const float* y_loc, const float* mean_vec, const float* y,
+                   const int* x_rows, const int* y_rows, int n, int S, int T, int off, int planes, void* g_in, int g_cs, void* rgb_in,
+                   int rgb_cs, void* depth_real, int depth_cs, float* target, void* stream);
+/* tdg_isamp_head_bn_fwd: generator A1's head d4 (:293 under the decoder's arg_scope: 1x1 conv cin -> 1, batch norm, tanh) on the
+ *   hw x hw concat [n,hw,hw,cs].  Phase 1, one block per image: z = w . cat + b, accumulated as tdg_xsamp_head_fwd accumulates
+ *   it, and the image's sums of z and z z in f64.  Phase 2: S, Q = the partials added in a fixed order (f64), N = n hw hw,
+ *   mean = S / N, var = max(Q / N - mean mean, 0) (biased), stats[0] = f32(mean), stats[1] = rstd = f32(1 / sqrt(var + eps)); then
+ *   in f32 zhat = fl(fl(z - stats[0]) * stats[1]), g = tanhf(fl(zhat + beta[0])) (no gamma).  g f32 [n,hw,hw], zhat f32 [n,hw,hw]
+ *   (kept for the backward pass), fake (channel 0 of D's fake depth input, channel stride fake_cs) = g rounded to the compute
+ *   dtype.  cin in {64,128,256,512}, cs % 8 == 0.  Workspace: 16 n bytes, 8-byte aligned (tdg_isamp_head_bn_workspace_bytes
+ *   covers both passes).  No atomics: two launches are bit-equal. */
+size_t tdg_isamp_head_bn_workspace_bytes(int n, int cin);
+int tdg_isamp_head_bn_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, const float* w, const float* b, const float* beta,
+                          float eps, float* g, float* zhat, float* stats, void* fake, int fake_cs, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* tdg_isamp_head_bn_bwd: from dL/dg (channel 0 of dfake) and the stored g, zhat and stats: dy = dL/dg * fl(1 - fl(g g));
+ *   dbeta[0] = f32(sum dy) (overwritten; the sum in f64 from per-image partials, a fixed order); m1 = f32(sum dy / N),
+ *   m2 = f32(sum dy zhat / N); dz = fl(rstd * fl(fl(dy - m1) - fl(zhat m2))) -- batch norm's backward pass without gamma --; then
+ *   tdg_xsamp_head_bwd's contract from dz on: dcat[p, c] = dz[p] * w[c] * mask(cat[p, c]) (the first writer of dcat),
+ *   dw[c] = sum_p dz[p] cat[p, c], db[0] = sum_p dz[p] (f32, overwritten; per-image partials summed in image order).
+ *   Workspace: tdg_isamp_head_bn_workspace_bytes(n, cin) = 16 n + 4 n (cin + 1) bytes, 8-byte aligned. */
+int tdg_isamp_head_bn_bwd(int dtype, const void* dfake, int fake_cs, const float* g, const float* zhat, const float* stats,
+                          const void* cat, int n, int hw, int cin, int cs, const float* w, int mask_mode, float leak, void* dcat,
+                          float* dw, float* db, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* tdg_isamp_rmse_grad: `--g_rmse` (:930-935): dfake[r dgs] += d rmse / d g[r], rmse = sqrt(mean(((g + 1) / 2 - (y + 1) / 2)^2)) over
+ *   the `rows` values, read from the device scalar rmse[0] (scal[1] of tdg_p2p_l1 on the same tensors).  g, y: channel 0 of
+ *   [-1,1] tensors of the compute dtype with row stride cs.  In f32, each operation rounded once, in this order:
+ *   k = 1 / fl(fl(4 * f32(rows)) * rmse);  t = fl(fl(g[r] - y[r]) * k);  dfake[r dgs] = round_to_dtype(fl(dfake[r dgs] + t)).
+ *   rmse == 0 is not guarded: k is then inf and the results are not finite, as the gradient of tf.sqrt at 0 is not. */
+int tdg_isamp_rmse_grad(int dtype, const void* g, const void* y, int rows, int cs, const float* rmse, void* dfake, int dgs,
+                        void* stream);
+/* tdg_isamp_zero_fraction: tf.nn.zero_fraction (`--g_sparsity`, :928) of the rows x c entries of x with row stride cs >= c (the
+ *   padding is not counted): out[0] = f32(count / (rows c)) with count the entries equal to zero (-0.0 counts), an exact integer,
+ *   and the division in f64.  Workspace: tdg_isamp_zero_fraction_workspace_bytes(), 8-byte aligned. */
+size_t tdg_isamp_zero_fraction_workspace_bytes(void);
+int tdg_isamp_zero_fraction(int dtype, const void* x, int rows, int c, int cs, float* out, void* workspace, size_t workspace_bytes,
+                            void* stream);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */
