@@ -123,6 +123,8 @@ SIGNATURES = {
     'tdg_isamp_rmse_grad': (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     'tdg_isamp_zero_fraction_workspace_bytes': (_sz, []),
     'tdg_isamp_zero_fraction': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'tdg_artist_mse_workspace_bytes': (_sz, []),
+    'tdg_artist_mse': (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -94,7 +94,7 @@ def build_parser():
     add('--beta1', type=float, default=0.9)
     add('--beta2', type=float, default=0.999)
     add = model_args.add_argument
-    add('--model', type=lambda s: s.lower(), default='fc', help='gan | wgan | iwgan | vae | cnn | any model plugin (pix2pix, paper_cgan, paper_sampler, paper_noise, paper_standalone, paper_baseline_standalone, mean_depth_estimator, experimental_sampler, improved_sampler).')
+    add('--model', type=lambda s: s.lower(), default='fc', help='gan | wgan | iwgan | vae | cnn | any model plugin (pix2pix, paper_cgan, paper_sampler, paper_noise, paper_standalone, paper_baseline_standalone, mean_depth_estimator, experimental_sampler, improved_sampler, artist).')
     add('--latent_size', type=int, default=200)
     # opt-ins for the reference's defects; every default reproduces the reference's effective behaviour
     add('--wgan_clip', type=float, default=0.0,
@@ -142,7 +142,7 @@ def parse_args(argv=None, display=False, warn=None):
             parser.add_argument(k, **v)
         args, leftover = parser.parse_known_args(leftover, namespace=args)
     # pass 3: the model plugin's flags (:158-162)
-    models = plugins.accepted_model_plugins()
+    models = plugins.trainable_model_plugins()
     if args.model in models:
         for k, v in models[args.model].arguments().items():
             kw = dict(v)

@@ -1,5 +1,5 @@
 """`--dataset synthetic`: the bench / smoke input of SURVEY.md section 8d (not in the reference, which has no way to run
-without its private data): uint8 U{0..255} / 255 images, or (rgb, depth) pairs for --model pix2pix (256 x 256) and
+without its private data): uint8 U{0..255} / 255 images, or (rgb, depth) pairs for --model pix2pix and --model artist (256 x 256) and
 --model paper_cgan / paper_sampler / paper_noise / paper_standalone / paper_baseline_standalone (65 x 65), or the 6-tuple of
 --model mean_depth_estimator (65 x 65 pair, two location channels, 53 x 70 originals) and of --model experimental_sampler (the same
 at 64 x 64), or the 2-, 4- or 5-tuple the `--g_arch` of --model improved_sampler reads (65 x 65 or 64 x 64)."""
@@ -23,7 +23,7 @@ class SyntheticDataset(DataPlugin):
     @staticmethod
     def get_source(args, sess):
         B = args.batch_size
-        if args.model == 'pix2pix':
+        if args.model in ('pix2pix', 'artist'):
             return SyntheticPairSource(4, B, sess.device, 256, 1234, sess.rank), 4 * B * sess.world_size, (256, 256, 3)
         if args.model in DEPTH_65:                           # the 65x65 crops of hem/examples/paper/*/*.config
             return SyntheticPairSource(4, B, sess.device, 65, 1234, sess.rank), 4 * B * sess.world_size, (65, 65, 3)

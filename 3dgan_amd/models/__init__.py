@@ -22,7 +22,8 @@ def model_funcs():
             'paper_noise': plugin_func('paper_noise'), 'paper_standalone': plugin_func('paper_standalone'),
             'paper_baseline_standalone': plugin_func('paper_baseline_standalone'),
             'mean_depth_estimator': plugin_func('mean_depth_estimator'),
-            'experimental_sampler': plugin_func('experimental_sampler'), 'improved_sampler': plugin_func('improved_sampler')}
+            'experimental_sampler': plugin_func('experimental_sampler'), 'improved_sampler': plugin_func('improved_sampler'),
+            'artist': plugin_func('artist')}
 
 
 def get_model(name):

@@ -78,9 +78,22 @@ def improved_model_plugins():
 
 
 def accepted_model_plugins():
-    """known_model_plugins() and the improved directory: what `--model` accepts."""
+    """known_model_plugins() and the improved directory (pinned; `--model` accepts trainable_model_plugins())."""
     found = known_model_plugins()
     found.update(improved_model_plugins())
+    return found
+
+
+def artist_model_plugins():
+    """The shared-encoder RGB and depth autoencoder (hem/models/artist.py): `3dgan_amd/models/artist/`.  It stays out of
+    accepted_model_plugins(), whose result is pinned like the unions before it; trainable_model_plugins() adds it."""
+    return search_for_plugins(os.path.join(_HERE, 'models', 'artist'), '3dgan_amd.models.artist', 'ModelPlugin')
+
+
+def trainable_model_plugins():
+    """accepted_model_plugins() and the artist directory: what `--model` accepts."""
+    found = accepted_model_plugins()
+    found.update(artist_model_plugins())
     return found
 
 
@@ -98,7 +111,7 @@ def data_plugins():
 
 def get_model(name):
     """hem/models/ModelPlugin.py:4-8: the plugin class registered under `name` (KeyError for an unknown name, as there)."""
-    return accepted_model_plugins()[name]
+    return trainable_model_plugins()[name]
 
 
 def get_dataset(name):

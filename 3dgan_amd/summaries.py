@@ -36,6 +36,13 @@ def montage(x, m=0, n=0):
     return out
 
 
+def jet(v):
+    """Piecewise-linear jet colours of v in [0, 1] -> [..., 3] in [0, 1] (blue, cyan, yellow, red): paper_fullimage.jet, restated
+    for the package (hem.montage's colorize=True)."""
+    v = np.clip(np.asarray(v, np.float64), 0.0, 1.0)[..., None]
+    return np.clip(1.5 - np.abs(4.0 * v - np.array([3.0, 2.0, 1.0])), 0.0, 1.0)
+
+
 def png_bytes(img01):
     """8-bit PNG (grey, RGB or RGBA by channel count) of an array [H, W, C] in [0, 1]; filter type 0 on every row."""
     a = np.asarray(img01, dtype=np.float64)

@@ -467,6 +467,25 @@ int tdg_isamp_rmse_grad(int dtype, const void* g, const void* y, int rows, int c
 size_t tdg_isamp_zero_fraction_workspace_bytes(void);
 int tdg_isamp_zero_fraction(int dtype, const void* x, int rows, int c, int cs, float* out, void* workspace, size_t workspace_bytes,
                             void* stream);
+/* ---- artist (hem/models/artist.py:71-83; 3dgan_amd/csrc/tdg_artist.hip) -------------------------------------------------------
+ * tdg_artist_mse: the whole-image loss of one decoder and its seed in ONE pass.  target: compact f32 [rows, c], the staged
+ *   batch in [0, 1]; h, seed: [rows, cs] in dtype, h the decoder's tanh output in [-1, 1].  1 <= c <= 4 (image planes),
+ *   cs % 8 == 0, h and seed 16-byte aligned (one 16-byte load of h per pixel), target 4-byte aligned: 16-byte loads of it
+ *   where its base is 16-byte aligned, 4-byte loads otherwise.  Per element, in f32, each operation rounded once, in this
+ *   order (hem.rescale: the target's round trip [0,1] -> [-1,1] -> [0,1], then h to [0,1]):
+ *     tm = fl(fl(2 t) - 1);  t01 = fl(fl(tm + 1) * 0.5);  h01 = fl(fl(h + 1) * 0.5);  d = fl(h01 - t01);
+ *     seed = round_to_dtype(fl(d * k)),  k = fl(1 / fl(rows c))   (the multiplications by 2 and 0.5 are exact)
+ *   -- d loss / d h: the 2 of the square and the 1/2 of the rescale cancel.  seed == NULL (mode 0, evaluation): the loss alone.
+ *   Channels [c, cs) of seed are NEVER written (as tdg_l1_loss leaves them).
+ *   scal[0] = f32(S / (rows c)), scal[1] = f32(sqrt(S / (rows c))), with S = the sum of the EXACT squares d d in f64 (the
+ *   product of two f32 fits f64), the division and the square root in f64: per thread, wave shuffle, the four waves, one f64
+ *   partial per block (a grid-stride loop over 1024-pixel tiles, four blocks per compute unit, at most 1024), then the
+ *   partials by one block in the same shape.  A fixed order and no atomics: two launches are bit-equal.  One launch plus the
+ *   finish.  Workspace: tdg_artist_mse_workspace_bytes() = 8192 bytes, 8-byte aligned; a short one is TDG_EWORKSPACE, a null
+ *   pointer, rows <= 0, c outside [1, min(4, cs)], cs % 8 != 0 or a misaligned pointer TDG_EINVAL, all before any launch. */
+size_t tdg_artist_mse_workspace_bytes(void);
+int tdg_artist_mse(int dtype, const float* target, const void* h, int rows, int c, int cs, void* seed, float* scal, void* workspace,
+                   size_t workspace_bytes, void* stream);
 /* tdg_cgan_eval_finish: scalars f64 [3][12], per set: the eight sums / batches, counts[k] / counts[3] for k < 3 (the final
  *   running percentages) and the batches (a set with no batch gives NaN).  mean_img / var_img f32 [hw] (both or neither):
  *   acc[28 + p] / acc[27] / unit and acc[28 + hw + p] / acc[27] / unit^2 -- unit = 10 turns the 10x depth into [0, 1]. */

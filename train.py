@@ -162,6 +162,8 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
                 real, fake = replica.samples(args.examples) if hasattr(replica, 'samples') else (None, None)
                 summaries.write_epoch(os.path.join(args.dir, 'summaries'), sess.global_epoch, status or {}, real, fake,
                                       args.examples)                                                   # models/gan.py:93-107
+                if hasattr(replica, 'write_montages'):                                                 # hem/models/artist.py:86-98
+                    replica.write_montages(os.path.join(args.dir, 'summaries'), sess.global_epoch)
                 ckpt.save(os.path.join(args.dir, 'checkpoint-{}.npz'.format(sess.global_epoch)), saved, sess)   # :329
                 ckpt.prune(args.dir, getattr(args, 'max_to_keep', 0))                                   # gen-2 --max_to_keep
     except Exception as e:
