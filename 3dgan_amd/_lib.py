@@ -42,6 +42,12 @@ class LaunchRecord(C.Structure):
     _fields_ = [('kernel', C.c_char * 64), ('ms', C.c_double), ('flops', C.c_double)]
 
 
+class SummaryJob(C.Structure):
+    """TdgSummaryJob (include/tdg.h)."""
+    _fields_ = [('ptr', C.c_void_p), ('rows', C.c_uint64), ('c', C.c_int32), ('cs', C.c_int32), ('dtype', C.c_int32),
+                ('scale', C.c_float)]
+
+
 _vp, _i, _f, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 _PD, _PE = C.POINTER(ConvDesc), C.POINTER(Epilogue)
 
@@ -125,6 +131,10 @@ SIGNATURES = {
     'tdg_isamp_zero_fraction': (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'tdg_artist_mse_workspace_bytes': (_sz, []),
     'tdg_artist_mse': (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_tensor_summary_limits': (_i, [C.POINTER(C.c_double)]),
+    'tdg_tensor_summary_result_bytes': (_sz, []),
+    'tdg_tensor_summary_workspace_bytes': (_sz, [_i, _u64]),
+    'tdg_tensor_summary': (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

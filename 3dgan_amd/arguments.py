@@ -70,6 +70,9 @@ def build_parser():
     add('--seed', type=int, help='Randomized each execution if not set.')
     add('--n_gpus', type=int, default=1, help='Number of GPUs (one replica process per GPU).')
     add('--profile', default=False, action='store_true', help='Write <dir>/profile.txt: the conv GEMM kernels of one training iteration (a dead flag in the reference).')
+    add('--event_files', default=False, action='store_true',
+        help='Write TensorBoard event files to <dir>/train: histograms, sparsity and means of layers, weights and gradients, '
+             'the losses, metrics and montages, at the cadence of hem/util/training.py:127-158 (chief only).')
     add('--check_numerics', default=False, action='store_true', help='Fail with the variable name on NaN/Inf gradients.')
     add('--precision', default='bf16', choices=['bf16', 'f32'],
         help='bf16 MFMA with f32 accumulate / master weights (throughput) or exact f32 (parity).')

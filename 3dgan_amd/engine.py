@@ -51,6 +51,7 @@ class Replica:
         # (--check_numerics keeps the graphs: the finite check runs between the captured bodies, never inside one)
         self.use_graphs = bool(getattr(args, 'use_graphs', True)) and sess.device.type == 'cuda'
         self._warm, self._graphs = set(), {}
+        self._summaries = None                     # write_event's K.TensorSummaries, built on its first call
 
     @classmethod
     def train_function(cls, x, args, sess=None):
@@ -92,6 +93,58 @@ class Replica:
         for store in self.stores():
             d.update(store.grads_dict())
         return d
+
+    # -- event files (summaries.py; train.py --event_files) ------------------------------------------
+    def summary_items(self):
+        """What an event records of this replica's device state, as K.TensorSummaries' items (tag, Act or tensor, scale):
+        every variable under `weights/<name>` (hem.summarize_weights_biases) and every gradient under `<name>/gradient`
+        (hem.summarize_gradients).  The gradient buckets of a multi-rank run hold the sum over the ranks -- the 1/n is folded
+        into the optimizer kernel -- so gradients are summarised with scale = 1 / world size.  A model with recorded
+        activations adds them under `g_activations/` / `d_activations/` (models/paper/paper_cgan.py)."""
+        items, inv = [], 1.0 / self.sess.world_size
+        stores = list({id(s): s for s in self.stores()}.values())
+        for store in stores:
+            items += [('weights/' + name, store.views[name], 1.0) for name in store.index]
+        for store in stores:
+            items += [(name + '/gradient', store.grad_views[name], inv) for name in store.index]
+        return items
+
+    def write_event(self, writer, step, losses=None):
+        """One event of the reference's merged summary op into `writer` (summaries.EventWriter) at `step`: per item of
+        summary_items() the histogram, plus `<tag>/sparsity` and `<tag>/mean` for an activation, the mean under the
+        gradient's own tag for a gradient and `<tag>/sparsity` for a weight (hem/ops/summaries.py:31-75); `loss/<key>` of
+        `losses` as scalar and histogram; the scalars of metrics(), where the replica has them; the montages of samples() /
+        montages() as images.  One tdg_tensor_summary launch and one device read cover all tensors.  Runs eagerly, between
+        steps.  The deviations from the reference are listed in summaries.py."""
+        from . import summaries as S
+        if self._summaries is None:
+            self._summaries = K.TensorSummaries(self.sess.device, self.summary_items())
+        for tag, s in self._summaries.run().items():
+            writer.histogram(tag, s, step)
+            if tag.endswith('/gradient'):
+                writer.scalar(tag, s.mean, step)
+            elif tag.startswith('weights/'):
+                writer.scalar(tag + '/sparsity', s.sparsity, step)
+            else:
+                writer.scalar(tag + '/sparsity', s.sparsity, step)
+                writer.scalar(tag + '/mean', s.mean, step)
+        for key, v in (losses or {}).items():
+            writer.scalar('loss/' + key, v, step)
+            writer.histogram('loss/' + key, S.host_summary([v]), step)
+        if hasattr(self, 'metrics'):
+            for name, values in self.metrics().items():
+                for key, v in values.items():
+                    writer.scalar('%s/%s' % (name, key), v, step)
+        examples = int(getattr(self.args, 'examples', 64))
+        if hasattr(self, 'montages'):
+            images = self.montages()
+        elif hasattr(self, 'samples'):
+            images = S.sample_montages(*self.samples(examples), examples)
+        else:
+            images = []
+        for name, img in images:
+            writer.image(name, S.png_bytes(img), img.shape[0], img.shape[1], img.shape[2], step)
+        writer.flush()
 
     # -- steps -------------------------------------------------------------------------------------
     def staging(self, *shapes):

@@ -6,6 +6,7 @@ channel stride (padding channels are kept at zero; see DESIGN.md "Data layout in
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -77,7 +78,9 @@ class Act:
         return self
 
     def get(self):
-        return self.buf.float().reshape(self.n, self.h, self.w, self.cs)[..., :self.c].cpu().numpy()
+        """The live channels as f32 [n, h, w, c] (a window's buffer ends behind its last live element)."""
+        live = torch.as_strided(self.buf, (self.rows, self.c), (self.cs, 1))
+        return live.float().reshape(self.n, self.h, self.w, self.c).cpu().numpy()
 
 
 def conv_desc(big, small, kh, kw, stride, pad_t, pad_l):
@@ -355,3 +358,67 @@ def in_bwd(ws, dh, u, n, c, scale, shift, stats, act, du, dscale, dshift, leak=0
 def add_act(dtype, a_ptr, b_ptr, n_elems, out_ptr, act=ACT_NONE, leak=0.2):
     """out = act(a + b) over n_elems elements of one layout."""
     _lib.call('tdg_add_act', dtype, a_ptr, b_ptr, n_elems, act, leak, out_ptr, stream())
+
+
+# ---------------------------------------------------------------------------------------------- tensor summaries
+_SUMMARY_LIMITS = {}
+RESULT_DTYPE = np.dtype([('num', '<u8'), ('zeros', '<u8'), ('nonfinite', '<u8'), ('min', '<f4'), ('max', '<f4'), ('sum', '<f8'),
+                         ('sum_squares', '<f8'), ('buckets', '<u8', (1551,))])       # the result record of include/tdg.h
+
+
+def summary_limits(device):
+    """The device copy of the histogram limits (tdg_tensor_summary_limits), one per device."""
+    t = _SUMMARY_LIMITS.get(device)
+    if t is None:
+        from .summaries import limits
+        t = _SUMMARY_LIMITS[device] = torch.from_numpy(limits().copy()).to(device)
+    return t
+
+
+class TensorSummaries:
+    """tdg_tensor_summary over a fixed set of device tensors.  `items`: (tag, Act or contiguous torch tensor, scale); an Act
+    is summarised over its live channels, a tensor as a flat array.  The job table, the result block and the workspace are
+    built once (the tensors of a replica never move); run() is one library call and ONE device-to-host copy."""
+
+    def __init__(self, device, items):
+        from ._lib import SummaryJob
+        lib = _lib.load()
+        self.tags, self._keep, jobs, total = [], [], [], 0
+        for tag, t, scale in items:
+            if isinstance(t, Act):
+                job = SummaryJob(t.buf.data_ptr(), t.rows, t.c, t.cs, t.dtype, scale)
+                self._keep.append(t.buf)
+            else:
+                if not t.is_contiguous() or t.dtype not in (torch.float32, torch.bfloat16):
+                    raise ValueError('TensorSummaries: %s must be a contiguous f32 or bf16 tensor' % tag)
+                job = SummaryJob(t.data_ptr(), 1, t.numel(), t.numel(), F32 if t.dtype == torch.float32 else BF16, scale)
+                self._keep.append(t)
+            if tag in self.tags:
+                raise ValueError('TensorSummaries: tag %s twice' % tag)
+            self.tags.append(tag)
+            jobs.append(job)
+            total += job.rows * job.c
+        if not jobs:
+            raise ValueError('TensorSummaries: no items')
+        table = (SummaryJob * len(jobs))(*jobs)
+        self.jobs = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+        self.limits = summary_limits(device)
+        self.live_elems = total
+        self.live_bytes = sum(j.rows * j.c * ELEM_SIZE[j.dtype] for j in jobs)
+        self.record_bytes = lib.tdg_tensor_summary_result_bytes()
+        if self.record_bytes != RESULT_DTYPE.itemsize:
+            raise _lib.TdgError('tdg_tensor_summary: records of %d bytes, %d expected' % (self.record_bytes, RESULT_DTYPE.itemsize))
+        self.results = torch.zeros(len(jobs) * self.record_bytes, dtype=torch.uint8, device=device)
+        self.ws = torch.zeros(max(lib.tdg_tensor_summary_workspace_bytes(len(jobs), total), 32), dtype=torch.uint8, device=device)
+
+    def launch(self):
+        _lib.call('tdg_tensor_summary', ptr(self.jobs), len(self.tags), ptr(self.limits), ptr(self.results), ptr(self.ws),
+                  self.ws.numel(), stream())
+
+    def run(self):
+        """{tag: summaries.TensorSummary}."""
+        from .summaries import TensorSummary
+        self.launch()
+        rec = self.results.cpu().numpy().view(RESULT_DTYPE)
+        return {tag: TensorSummary(r['num'], r['zeros'], r['nonfinite'], r['min'], r['max'], r['sum'], r['sum_squares'], r['buckets'])
+                for tag, r in zip(self.tags, rec)}

@@ -263,22 +263,28 @@ class artist(ModelPlugin, engine.Replica):
         a = (self.eval_acc / n_batches).cpu().tolist()
         return {'x_hat_loss': a[0], 'y_hat_loss': a[2], 'y_hat_rmse': a[3], 'images': n_batches * self.B, 'n_batches': n_batches}
 
+    def montages(self):
+        """[(name, image [H, W, C] in [0, 1])] of write_montages' four montages (also the image summaries of an event)."""
+        self._run('a_forward', self._forward_body)
+        x_hat, y_hat = self._outputs01()
+        n = int(math.floor(math.sqrt(min(int(self.args.examples), self.B))))
+        if n < 1:
+            raise ValueError('write_montages: --examples %r leaves no image' % self.args.examples)
+        out = []
+        for name, t, colorize in (('x', self.x_stage, False), ('y', self.y_stage, True), ('x_hat', x_hat, False), ('y_hat', y_hat, True)):
+            a = t[:n * n].cpu().numpy()
+            out.append((name, summaries.montage(summaries.jet(a[..., 0]) if colorize else a, n, n)))
+        return out
+
     def write_montages(self, directory, epoch):
         """The four montages of :86-98 -- x, y (jet colours), x_hat, y_hat (jet colours) -- of the first `--examples` images of
         the batch in the staging buffers (the last one fetched), in an n x n grid, n = floor(sqrt(examples)), as
         `montage-<name>-<epoch>.png`.  The reconstructions come from a forward pass of their own on that batch.  Returns the
         paths.  DEVIATION: the reference hands hem.montage all `examples` images with height = width = n; where examples is not
         a square the grid holds the first n n of them."""
-        self._run('a_forward', self._forward_body)
-        x_hat, y_hat = self._outputs01()
-        n = int(math.floor(math.sqrt(min(int(self.args.examples), self.B))))
-        if n < 1:
-            raise ValueError('write_montages: --examples %r leaves no image' % self.args.examples)
         os.makedirs(directory, exist_ok=True)
         written = []
-        for name, t, colorize in (('x', self.x_stage, False), ('y', self.y_stage, True), ('x_hat', x_hat, False), ('y_hat', y_hat, True)):
-            a = t[:n * n].cpu().numpy()
-            img = summaries.montage(summaries.jet(a[..., 0]) if colorize else a, n, n)
+        for name, img in self.montages():
             path = os.path.join(directory, 'montage-%s-%04d.png' % (name, epoch))
             summaries.write_png(path, img)
             written.append(path)

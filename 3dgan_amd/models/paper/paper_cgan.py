@@ -258,6 +258,18 @@ class GeneratorReplica(engine.Replica):
                       K.ptr(self.head_ws), self.head_ws.numel() * 4, K.stream())
         self.G.backward()
 
+    # ---- event files ---------------------------------------------------------------------------------------
+    def summary_items(self):
+        """engine.Replica's weights and gradients, and the generator's activations under `g_activations/<scope>/<layer>`
+        (hem/models/paper_cgan.py:170,172): the U-Net's encoder and decoder outputs -- channel windows of its zero-copy concat
+        buffers -- and the head's g, which exists as the 29x29 crop only.  They hold what the last generator pass left."""
+        items = engine.Replica.summary_items(self)
+        G = self.G
+        items += [('g_activations/%s/%s' % (self.enet.name, self.enet.layers[k - 1].name), G.e_h[k], 1.0) for k in range(1, G.n + 1)]
+        items += [('g_activations/%s/%s' % (self.dec_net.name, self.dec_net.layers[i - 1].name), G.d_h[i], 1.0) for i in range(1, G.nd + 1)]
+        items.append(('g_activations/%s/%s' % (self.dec_net.name, self.head.name), self.fake.window(0, 1), 1.0))
+        return items
+
     # ---- evaluation ----------------------------------------------------------------------------------------
     def metrics(self):
         """The Eigen-2014 sets `metrics_y_hat` and `metrics_y_0` (:171-172, :447-478) of the last loss fetch's batch.
@@ -527,6 +539,15 @@ class CganReplica(GeneratorReplica):
         mp2 = self.version == 2
         return (self.Dd.x.ptr(0), self.Dd.x.cs, self.Dd.x.ptr(self.B) if mp2 else None,
                 self.Dr.x.window(3, 1).ptr(0) if mp2 else None, self.Dr.x.cs)
+
+    def summary_items(self):
+        """GeneratorReplica's, and under `d_activations/<scope>/<layer>` every layer output of the critic's three paths
+        (hem/models/paper_cgan.py:171,173): the rgb path over the B images, the depth and combined paths over the real and
+        the fake half together."""
+        items = GeneratorReplica.summary_items(self)
+        for net in (self.Dr, self.Dd, self.Dc):
+            items += [('d_activations/%s/%s' % (net.net.name, L.spec.name), L.out if L.rowdot else L.h, 1.0) for L in net.layers]
+        return items
 
     # ---- pieces ------------------------------------------------------------------------------------------
     def _d_forward(self):

@@ -629,6 +629,39 @@ int tdg_random_normal_dev(int dtype, uint64_t seed, uint64_t stream_id, int32_t*
 int tdg_random_uniform_f32_dev(uint64_t seed, uint64_t stream_id, int32_t* draw_dev, size_t n, float* out,
                                void* stream);
 
+/* ---- tensor summaries for the training event files (hem/ops/summaries.py:31-75: per layer, gradient and weight a
+ *      tf.summary.histogram, tf.nn.zero_fraction and tf.reduce_mean; called at hem/models/paper_cgan.py:166-177 and
+ *      hem/models/artist.py:99-103) for a whole table of tensors at once.
+ *      One job is one tensor of rows x c live elements with row stride cs (elements); a flat array is rows = 1, c = cs = n.
+ *      Any base alignment the dtype allows is legal, and only live elements are read.  The element value is
+ *      v = f32(x) * scale (one f32 multiply; gradients of a multi-rank run are summarised with scale = 1 / world size).
+ *      Per job the result record of tdg_tensor_summary_result_bytes() bytes holds, in this order:
+ *        uint64 num, zeros (v == 0, both signs), nonfinite (NaN, +-Inf);  float min, max;  double sum, sum_squares
+ *        (of (double)v and (double)v * (double)v);  uint64 bucket[1551].
+ *      Non-finite elements count in `nonfinite` only; with no finite element min, max and the sums are 0.
+ *      Buckets are TensorFlow's default histogram: element v adds to bucket b = the number of limits <= (double)v of the
+ *      1551 limits [-DBL_MAX, -pos reversed, 0, pos, DBL_MAX], pos = 1e-12 * 1.1^k by repeated f64 multiplication while
+ *      below 1e20.  tdg_tensor_summary_limits (host, no GPU work) fills that table; the caller keeps a device copy and hands
+ *      it to every launch.
+ *      tdg_tensor_summary: `jobs_dev`, `limits_dev`, `results_dev` (njobs records) and `workspace` (at least
+ *      tdg_tensor_summary_workspace_bytes(njobs, total live elements) bytes) are device memory.  Counts are exact; the sums
+ *      are combined in a fixed order, so two launches on the same input are bit-equal in every field.  The entry reads the
+ *      job table back to validate it and to size its grid -- it synchronises `stream`, unlike every other entry, and must not
+ *      be called inside a captured body -- then enqueues a fixed three operations whatever njobs is.  A bad argument or job is
+ *      a status, and nothing is written. */
+typedef struct TdgSummaryJob {
+  const void* ptr;
+  uint64_t rows;
+  int32_t c, cs;
+  int32_t dtype;            /* TDG_F32 | TDG_BF16 */
+  float scale;
+} TdgSummaryJob;
+int tdg_tensor_summary_limits(double* out);
+size_t tdg_tensor_summary_result_bytes(void);
+size_t tdg_tensor_summary_workspace_bytes(int njobs, uint64_t total_elems);
+int tdg_tensor_summary(const TdgSummaryJob* jobs_dev, int njobs, const double* limits_dev, void* results_dev, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- input pipeline, host side (no GPU work): PNG scanline reconstruction (filter types 0-4 of the PNG
  *      specification) after the caller has inflated the IDAT stream -- what tf.image.decode_png does for the
  *      reference's nyuv2 / floorplan records (hem/data/nyuv2.py:152-153, data.py:15).  `filtered` holds `rows`

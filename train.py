@@ -136,9 +136,13 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
     saved = replica if saved is None else saved
     current_epoch = sess.global_epoch
     status = None
+    # --event_files: <dir>/train/events.out.tfevents.*, the reference's summary_writers['train'] (hem/util/training.py:127-158)
+    events = summaries.EventWriter(os.path.join(args.dir, 'train')) if chief and getattr(args, 'event_files', False) else None
     if sess.global_step == 0 and chief:
         message('Generating baseline checkpoint...')
         ckpt.save(os.path.join(args.dir, 'checkpoint-0.npz'), saved, sess)                             # train.py:288-291
+        if events is not None:
+            replica.write_event(events, sess.global_step, {})                                          # training.py:129-130
     if chief:
         message('Starting training...')
     try:
@@ -157,7 +161,11 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
                     replica.use_graphs = graphs
                 if chief:
                     pbar.set_postfix(util.format_for_terminal(dict(status), prev_status))
+                if events is not None and summaries.event_due(epoch, i, iter_per_epoch):               # training.py:142-150
+                    replica.write_event(events, sess.global_step, status)
             sess.global_epoch += 1                                                                     # train.py:322
+            if events is not None:
+                replica.write_event(events, sess.global_step, status or {})                            # training.py:157-159
             if chief:
                 real, fake = replica.samples(args.examples) if hasattr(replica, 'samples') else (None, None)
                 summaries.write_epoch(os.path.join(args.dir, 'summaries'), sess.global_epoch, status or {}, real, fake,
@@ -166,6 +174,8 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
                     replica.write_montages(os.path.join(args.dir, 'summaries'), sess.global_epoch)
                 ckpt.save(os.path.join(args.dir, 'checkpoint-{}.npz'.format(sess.global_epoch)), saved, sess)   # :329
                 ckpt.prune(args.dir, getattr(args, 'max_to_keep', 0))                                   # gen-2 --max_to_keep
+        if events is not None:
+            events.close()
     except Exception as e:
         # gen-2's convention (hem/util/training.py:173-175): report and leave with -1, the status repeat.sh restarts on
         # (it resumes from the newest checkpoint in --dir); the library's status text travels in the exception
