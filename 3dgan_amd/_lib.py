@@ -48,6 +48,12 @@ class SummaryJob(C.Structure):
                 ('scale', C.c_float)]
 
 
+class MontageJob(C.Structure):
+    """TdgMontageJob (include/tdg.h)."""
+    _fields_ = [('ptr', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('c', C.c_int32), ('cs', C.c_int32), ('dtype', C.c_int32),
+                ('reserved', C.c_int32), ('out_offset', C.c_uint64)]
+
+
 _vp, _i, _f, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 _PD, _PE = C.POINTER(ConvDesc), C.POINTER(Epilogue)
 
@@ -135,6 +141,7 @@ SIGNATURES = {
     'tdg_tensor_summary_result_bytes': (_sz, []),
     'tdg_tensor_summary_workspace_bytes': (_sz, [_i, _u64]),
     'tdg_tensor_summary': (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    'tdg_activation_montage': (_i, [_vp, _i, _vp, _sz, _vp, _vp]),
     'tdg_cgan_full_gather': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'tdg_cgan_full_store': (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
     'tdg_cgan_full_blend': (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp]),

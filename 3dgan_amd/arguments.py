@@ -73,6 +73,9 @@ def build_parser():
     add('--event_files', default=False, action='store_true',
         help='Write TensorBoard event files to <dir>/train: histograms, sparsity and means of layers, weights and gradients, '
              'the losses, metrics and montages, at the cadence of hem/util/training.py:127-158 (chief only).')
+    add('--event_montages', default=False, action='store_true',
+        help='With --event_files: every event also carries the activation montages of hem.summarize_layers(montage=True), '
+             'one grey image per recorded layer.')
     add('--check_numerics', default=False, action='store_true', help='Fail with the variable name on NaN/Inf gradients.')
     add('--precision', default='bf16', choices=['bf16', 'f32'],
         help='bf16 MFMA with f32 accumulate / master weights (throughput) or exact f32 (parity).')
@@ -86,7 +89,13 @@ def build_parser():
         help='Discriminator steps per generator step (default 5; 1 for --model pix2pix, its plugin default).')
     add('--max_to_keep', type=int, default=0, help='gen-2: most recent checkpoints to keep; 0 keeps every one.')
     add('--test_epochs', nargs='*', default=[], type=int,
-        help='gen-2: epochs at which to run the test split (accepted; the test pass belongs to the thesis harness).')
+        help='gen-2: epochs (counted from 1) after which the test split runs like the validation pass, into <dir>/test and '
+             'summaries/test.csv (hem/util/training.py:167-169); needs --validation.')
+    add('--validation', default=False, action='store_true',
+        help='gen-2: after every epoch run the validate split without training on it (hem.inference): loss means into '
+             'summaries/validation.csv and, with --event_files, one event into <dir>/validate; at start the mean / variance '
+             'images of the train and validate splits.  Models with a validation pass only; --n_gpus 1.')
+    add('--validation_batches', type=int, default=None, help='Batches of a validation / test pass (default: split size // batch size).')
     add = optimizer_args.add_argument
     add('--optimizer', type=lambda s: s.lower(), default='rmsprop')
     add('--lr', type=float, default=0.001)
@@ -165,7 +174,23 @@ def parse_args(argv=None, display=False, warn=None):
     args.unknown_args = leftover
     if args.n_disc_train is None:                        # train.py:107-111 default 5 (plugins bring their own)
         args.n_disc_train = 5
+    check_validation(args)
     if display:
         for a in vars(args):
             print('    {} = {}'.format(a, getattr(args, a)))
     return args
+
+
+def check_validation(args):
+    """--validation / --event_montages are refused here, before anything trains or a second process starts."""
+    if args.event_montages and not args.event_files:
+        raise SystemExit('--event_montages needs --event_files: the montages are images of the event files')
+    if args.validation_batches is not None and args.validation_batches < 1:
+        raise SystemExit('--validation_batches must be >= 1')
+    if not args.validation:
+        return
+    if args.n_gpus > 1:
+        raise SystemExit('--validation with --n_gpus %d: the validation pass runs on one rank only (use --n_gpus 1)' % args.n_gpus)
+    cls = plugins.trainable_model_plugins().get(args.model)
+    if cls is None or not getattr(cls, 'has_validation', lambda: False)():
+        raise SystemExit('--validation: --model %s has no validation pass (no observe / validation_losses)' % args.model)

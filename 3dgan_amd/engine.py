@@ -52,6 +52,7 @@ class Replica:
         self.use_graphs = bool(getattr(args, 'use_graphs', True)) and sess.device.type == 'cuda'
         self._warm, self._graphs = set(), {}
         self._summaries = None                     # write_event's K.TensorSummaries, built on its first call
+        self._montages = None                      # write_event's K.ActivationMontages (False: the model has no items)
 
     @classmethod
     def train_function(cls, x, args, sess=None):
@@ -109,13 +110,43 @@ class Replica:
             items += [(name + '/gradient', store.grad_views[name], inv) for name in store.index]
         return items
 
-    def write_event(self, writer, step, losses=None):
+    def montage_items(self):
+        """The activations whose montage an event records with `montages=True`, as K.ActivationMontages' items (tag, Act):
+        hem.summarize_layers(..., montage=True) lays the channels of image 0 of every recorded layer out as one grey image.
+        None by default; the depth family (models/paper/paper_cgan.py) returns its recorded activations."""
+        return []
+
+    def _activation_montage_items(self):
+        """`<tag>/montage` for every activation of summary_items() that is an Act."""
+        return [(tag + '/montage', t) for tag, t, _ in self.summary_items()
+                if tag.startswith(('g_activations/', 'd_activations/')) and isinstance(t, K.Act)]
+
+    @classmethod
+    def has_validation(cls):
+        """Whether validation_losses / observe exist (train.py --validation asks before it trains)."""
+        return False
+
+    def validation_losses(self, batch):
+        """The loss dict of one held-out batch from a forward-only pass: no gradient, no optimizer step."""
+        raise NotImplementedError('model %s has no validation pass (validation_losses)' % self._model_name())
+
+    def observe(self, batch):
+        """The gradient bodies of one step on a held-out batch without the optimizer's half: activations, gradients and
+        metrics of that batch for write_event, every variable untouched."""
+        raise NotImplementedError('model %s has no validation pass (observe)' % self._model_name())
+
+    def _model_name(self):
+        return getattr(self, 'name', None) or getattr(self.args, 'model', None) or type(self).__name__
+
+    def write_event(self, writer, step, losses=None, montages=False):
         """One event of the reference's merged summary op into `writer` (summaries.EventWriter) at `step`: per item of
         summary_items() the histogram, plus `<tag>/sparsity` and `<tag>/mean` for an activation, the mean under the
         gradient's own tag for a gradient and `<tag>/sparsity` for a weight (hem/ops/summaries.py:31-75); `loss/<key>` of
         `losses` as scalar and histogram; the scalars of metrics(), where the replica has them; the montages of samples() /
-        montages() as images.  One tdg_tensor_summary launch and one device read cover all tensors.  Runs eagerly, between
-        steps.  The deviations from the reference are listed in summaries.py."""
+        montages() as images.  One tdg_tensor_summary launch and one device read cover all tensors.  With `montages`, one
+        tdg_activation_montage call and one more read supply a grey PNG per item of montage_items() under
+        `<tag>/image/0`; the kernel's bytes are the PNG's samples.  Runs eagerly, between steps.  The deviations from the
+        reference are listed in summaries.py."""
         from . import summaries as S
         if self._summaries is None:
             self._summaries = K.TensorSummaries(self.sess.device, self.summary_items())
@@ -144,6 +175,13 @@ class Replica:
             images = []
         for name, img in images:
             writer.image(name, S.png_bytes(img), img.shape[0], img.shape[1], img.shape[2], step)
+        if montages:
+            if self._montages is None:
+                items = self.montage_items()
+                self._montages = K.ActivationMontages(self.sess.device, items) if items else False
+            if self._montages:
+                for tag, (img, _, _) in self._montages.run().items():
+                    writer.image(tag, S.png_bytes_u8(img), img.shape[0], img.shape[1], 1, step)
         writer.flush()
 
     # -- steps -------------------------------------------------------------------------------------

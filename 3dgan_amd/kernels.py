@@ -422,3 +422,51 @@ class TensorSummaries:
         rec = self.results.cpu().numpy().view(RESULT_DTYPE)
         return {tag: TensorSummary(r['num'], r['zeros'], r['nonfinite'], r['min'], r['max'], r['sum'], r['sum_squares'], r['buckets'])
                 for tag, r in zip(self.tags, rec)}
+
+
+# ---------------------------------------------------------------------------------------------- activation montages
+class ActivationMontages:
+    """tdg_activation_montage over a fixed set of activations.  `items`: (tag, Act) pairs; each job is image 0 of its Act.  The
+    job table and the output block -- every job's (lo, hi) pair, then the montages back to back -- are built once; run() is one
+    library call and ONE device-to-host copy."""
+
+    def __init__(self, device, items):
+        from ._lib import MontageJob
+        from .summaries import factorization
+        self.tags, self.shapes, self._keep, jobs = [], [], [], []
+        for tag, a in items:
+            if not isinstance(a, Act):
+                raise ValueError('ActivationMontages: %s is not an Act' % tag)
+            if tag in self.tags:
+                raise ValueError('ActivationMontages: tag %s twice' % tag)
+            self.tags.append(tag)
+            self._keep.append(a.buf)
+            jobs.append(MontageJob(a.buf.data_ptr(), a.h, a.w, a.c, a.cs, a.dtype, 0, 0))
+            m, n = factorization(a.c)
+            self.shapes.append((n * a.h, m * a.w))
+        if not jobs:
+            raise ValueError('ActivationMontages: no items')
+        self.head = 8 * len(jobs)                            # the result block: njobs x (f32 lo, f32 hi)
+        off = 0
+        for job, (rows, cols) in zip(jobs, self.shapes):
+            job.out_offset = off
+            off += rows * cols
+        self.out_bytes = off
+        table = (MontageJob * len(jobs))(*jobs)
+        self.jobs = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+        self.block = torch.zeros(self.head + self.out_bytes, dtype=torch.uint8, device=device)
+
+    def launch(self):
+        _lib.call('tdg_activation_montage', ptr(self.jobs), len(self.tags), ptr(self.block, self.head), self.out_bytes, ptr(self.block),
+                  stream())
+
+    def run(self):
+        """{tag: (uint8 [n*H, m*W], min, max)}."""
+        self.launch()
+        host = self.block.cpu().numpy()
+        rng = host[:self.head].view('<f4').reshape(-1, 2)
+        out, off = {}, self.head
+        for tag, (rows, cols), (lo, hi) in zip(self.tags, self.shapes, rng):
+            out[tag] = (host[off:off + rows * cols].reshape(rows, cols), float(lo), float(hi))
+            off += rows * cols
+        return out

@@ -270,6 +270,11 @@ class GeneratorReplica(engine.Replica):
         items.append(('g_activations/%s/%s' % (self.dec_net.name, self.head.name), self.fake.window(0, 1), 1.0))
         return items
 
+    def montage_items(self):
+        """hem.summarize_layers(..., montage=True) (hem/models/paper_cgan.py:172-173): image 0 of every activation of
+        summary_items(), 1x1 layers included, under `<its tag>/montage`."""
+        return self._activation_montage_items()
+
     # ---- evaluation ----------------------------------------------------------------------------------------
     def metrics(self):
         """The Eigen-2014 sets `metrics_y_hat` and `metrics_y_0` (:171-172, :447-478) of the last loss fetch's batch.
@@ -618,6 +623,48 @@ class CganReplica(GeneratorReplica):
     def _g_apply(self):
         self.g_opt.step(self._scale)
         self.G.repack()
+
+    # ---- held-out batches (train.py --validation; hem.inference, hem/util/misc.py:85-93) ---------------------------
+    _STEP_BODIES = ('d_step', 'g_step', '_d_grads', '_g_grads', '_d_forward', '_loss', '_losses')
+
+    @classmethod
+    def has_validation(cls):
+        """validation_losses / observe are built from CganReplica's own step bodies: a subclass that replaces one of them
+        (models/sampler/) has no validation pass until it states its own."""
+        return all(getattr(cls, m) is getattr(CganReplica, m) for m in CganReplica._STEP_BODIES)
+
+    def _need_validation(self, what):
+        if not self.has_validation():
+            raise NotImplementedError('model %s has no validation pass (%s): it replaces step bodies of the depth cGAN'
+                                      % (self._model_name(), what))
+
+    def _forward_losses(self):
+        """_g_grads without its backward half: inputs, generator, critic on both halves, the loss kernel."""
+        self._clip(self.g_store, self.G.repack)
+        self._inputs(self.ybar, self.crop)
+        self._generate(self.ybar, self.yhat)
+        self._d_forward()
+        self._loss(2)
+
+    def validation_losses(self, batch):
+        """The loss dict of _losses() for one held-out batch, from a forward-only captured body.  Variables, optimizer
+        slots, packed filters and step counters stay as they are (--wgan_clip's clamp, where asked for, runs as in the G
+        step: it is idempotent).  metrics() then reports this batch."""
+        self._need_validation('validation_losses')
+        self._stage(batch)
+        self._run('v_losses', self._forward_losses)
+        return self._losses()
+
+    def observe(self, batch):
+        """The reference's summary op on a fed batch: the D and then the G gradient body of one step on `batch`, without
+        either optimizer half, without the exchange between ranks and without a global_step increment.  Afterwards the
+        activation, gradient and metric buffers hold this batch's values for write_event; variables, optimizer slots, packed
+        filters and step counters stay as they are (--wgan_clip as in validation_losses).  Returns the losses."""
+        self._need_validation('observe')
+        self._stage(batch)
+        self._run('d_grads', self._d_grads)
+        self._run('g_grads', self._g_grads)
+        return self._losses()
 
     def _losses(self):
         s = self.sess.report_scalars(self.scal, mean=getattr(self.args, 'mean_loss', False)).cpu().tolist()

@@ -18,11 +18,19 @@ read_events / get_tag_values restate the reference's readers.  Which tensors a r
 and write_event.
 DEVIATION: TensorFlow uniquifies a tag that is used twice (`linear_rmse_1`, `generator/encoder_1`); tags here are the
     names themselves (`g_activations/generator/encoder/e1`), never suffixed.
-DEVIATION: the activations recorded are those the last train() left in the replica's buffers; the reference runs a forward
-    pass of its own, on a fresh batch, for every event.
-DEVIATION: only the depth family of models/paper/paper_cgan.py records activations; every other model records losses,
-    weights and gradients.
-DEVIATION: the activation montages of summarize_layers(montage=True) are not written.
+Activation montages (`--event_montages`): hem.summarize_layers(..., montage=True) lays the channels of image 0 of every
+recorded layer out with hem.montage and hands the result to tf.summary.image; tdg_activation_montage
+(kernels.ActivationMontages) computes those bytes on the device, write_event(montages=True) wraps them into grey PNGs under
+`<tag>/montage/image/0`.  Validation and test passes (`train.py --validation`, `--test_epochs`): hem.inference's events go to
+`<dir>/validate` and `<dir>/test`, of a held-out batch run through Replica.observe.
+DEVIATION: the activations recorded in a TRAIN event are those the last train() left in the replica's buffers; the reference
+    runs a forward pass of its own, on a fresh batch, for every event.  (A validate / test event is of its own fresh batch.)
+DEVIATION: only the depth family of models/paper/paper_cgan.py records activations and their montages; every other model
+    records losses, weights and gradients.
+DEVIATION: tf.summary.image's value rule is restated from TensorFlow 1.x's NormalizeFloatImage (include/tdg.h); the PNG is
+    this package's encoder's (zlib level 6, filter type 0), not libpng's: the decoded samples are the same, the file bytes not.
+DEVIATION: the reference's test call has the wrong arity (training.py:168, paper_train.py:106) and never ran; the test pass
+    here has the validation call's shape and is fed the validation mean image.
 DEVIATION: get_all_events never appends a histogram it finds (hem/ops/summaries.py:215-217 only creates the tag's list);
     read_events appends it.
 """
@@ -73,7 +81,19 @@ def png_bytes(img01):
     h, w, c = a.shape
     if c not in (1, 3, 4):
         raise ValueError('png: %d channels' % c)
-    u8 = np.clip(np.rint(a * 255.0), 0, 255).astype(np.uint8)
+    return png_bytes_u8(np.clip(np.rint(a * 255.0), 0, 255).astype(np.uint8))
+
+
+def png_bytes_u8(u8):
+    """8-bit PNG of a uint8 array [H, W] or [H, W, C] as it stands: the samples are the array's bytes."""
+    u8 = np.asarray(u8)
+    if u8.dtype != np.uint8:
+        raise ValueError('png: %s samples, expected uint8' % u8.dtype)
+    if u8.ndim == 2:
+        u8 = u8[:, :, None]
+    h, w, c = u8.shape
+    if c not in (1, 3, 4):
+        raise ValueError('png: %d channels' % c)
     raw = b''.join(b'\x00' + u8[r].tobytes() for r in range(h))
 
     def chunk(tag, data):

@@ -662,6 +662,35 @@ size_t tdg_tensor_summary_workspace_bytes(int njobs, uint64_t total_elems);
 int tdg_tensor_summary(const TdgSummaryJob* jobs_dev, int njobs, const double* limits_dev, void* results_dev, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- activation montages for the training event files (hem.summarize_layers(..., montage=True), hem/ops/summaries.py:31-48:
+ *      hem.montage (:139-181) of image 0 of a layer, through tf.summary.image) for a whole table of activations at once.
+ *      One job is image 0 of an NHWC activation: `ptr` is pixel (0,0), channel 0 of the live window, h x w pixels of c live
+ *      channels, pixel stride cs (elements, cs >= c).  Any base alignment the dtype allows is legal, only the live channels
+ *      are read, and nothing behind the last live element of the last pixel.
+ *      Layout: (m, n) = factorization(c), m the largest divisor of c with m * m <= c, n = c / m.  The job's montage is n*h rows
+ *      by m*w columns of one byte each, row-major from `out_offset` of the packed output; channel j*m + i lands at block row j,
+ *      block column i.
+ *      Values (TensorFlow's NormalizeFloatImage): lo and hi are the min and max over the finite elements of the image (bf16
+ *      widened to f32).  If lo < 0: M = max(|lo|, |hi|), scale = M < 1e-6f ? 0 : 127.0f / M, offset = 128.0f; otherwise
+ *      scale = hi < 1e-6f ? 0 : 255.0f / hi, offset = 0.  A finite pixel v becomes (uint8) min(v * scale + offset, 255.0f): one
+ *      IEEE f32 divide, one f32 multiply, one f32 add (not fused), truncation.  A non-finite pixel becomes 255; an image
+ *      with no finite element is all 255 and reports lo = hi = 0.
+ *      tdg_activation_montage: `jobs_dev`, `out_dev` (out_bytes bytes) and `results_dev` (njobs x {float lo, hi}) are device
+ *      memory.  Bytes of the output outside every job's n*h*m*w region are not written.  Two launches on the same input are
+ *      bit-equal.  Like tdg_tensor_summary the entry reads the job table back to validate it -- it synchronises `stream` and
+ *      must not be called inside a captured body -- then enqueues two launches whatever njobs is.  A bad job (null pointer,
+ *      non-positive dims, cs < c, unknown dtype, a region that overlaps another or runs past out_bytes) is a status, and
+ *      nothing is written. */
+typedef struct TdgMontageJob {
+  const void* ptr;
+  int32_t h, w, c, cs;
+  int32_t dtype;            /* TDG_F32 | TDG_BF16 */
+  int32_t reserved;
+  uint64_t out_offset;
+} TdgMontageJob;
+int tdg_activation_montage(const TdgMontageJob* jobs_dev, int njobs, void* out_dev, size_t out_bytes, float* results_dev,
+                           void* stream);
+
 /* ---- input pipeline, host side (no GPU work): PNG scanline reconstruction (filter types 0-4 of the PNG
  *      specification) after the caller has inflated the IDAT stream -- what tf.image.decode_png does for the
  *      reference's nyuv2 / floorplan records (hem/data/nyuv2.py:152-153, data.py:15).  `filtered` holds `rows`

@@ -52,17 +52,7 @@ def parse_args(argv=None):
 
 def open_split(args, sess, split):
     """(source, examples) of one split: next_batch() -> (x [B,65,65,3], y [B,65,65,1]) in [0, 1] on the device."""
-    if args.dataset == 'synthetic':
-        data = importlib.import_module('3dgan_amd.data')
-        src = data.SyntheticPairSource(SYNTH_BATCHES, args.batch_size, sess.device, 65, 1234 + SPLITS.index(split), sess.rank)
-        return src, SYNTH_BATCHES * args.batch_size
-    name = importlib.import_module('3dgan_amd.arguments').dataset_plugin_name(args.dataset)
-    if name != 'nyuv2':
-        raise SystemExit('paper_metrics: --dataset nyuv2 or synthetic (got %r)' % args.dataset)
-    if not getattr(args, 'random_crop', None) or tuple(args.random_crop) != (65, 65):
-        raise SystemExit('paper_metrics: the model reads 65 x 65 crops (--random_crop 65 65)')
-    src, n, _ = importlib.import_module('3dgan_amd.plugins').data_plugins()[name].get_source(args, sess, split=split)
-    return src, n
+    return importlib.import_module('3dgan_amd.datasets').open_split(args, sess, split, who='paper_metrics')
 
 
 def batches_of(args, examples):

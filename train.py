@@ -125,6 +125,70 @@ def resume(replica, args, sess, chief):
     replica.refresh()
 
 
+class Validation:
+    """--validation: what paper_train.py does around its training loop with held-out data.  At start (:53-60) the mean and
+    variance depth images of the train and validate splits go to `--dir` as PNG files and the training mean becomes the
+    replica's mean image, so that train events carry `metrics_y_mean`.  run() is hem.inference (hem/util/misc.py:85-93) for
+    one split: the loss means of `validation_losses` over the split's batches into `summaries/<name>.csv` and, with
+    --event_files, one event of `observe(next batch)` into `<dir>/<split>` under the split's mean image.  Every split has a
+    source of its own -- the moments read a second train source -- so the training source is never consumed.
+    The reference's test call (paper_train.py:106, training.py:168) has the wrong arity and cannot run; the test pass here has
+    the validation call's shape and is fed the validation mean image."""
+    WHO = 'train.py --validation'
+
+    def __init__(self, replica, args, sess):
+        datasets = importlib.import_module('3dgan_amd.datasets')
+        summaries = importlib.import_module('3dgan_amd.summaries')
+        import numpy as np
+        self.replica, self.args, self.sess = replica, args, sess
+        self.sources, self.writers, self.means = {}, {}, {}
+        for split in ['validate'] + (['test'] if args.test_epochs else []):
+            src, n = datasets.open_split(args, sess, split, self.WHO)
+            self.sources[split] = (src, args.validation_batches or max(1, n // args.batch_size))
+        if hasattr(replica, 'dataset_moments'):
+            for split, name in (('train', 'training'), ('validate', 'validation')):
+                message('Calculating mean depth image for {}...'.format(name))
+                src, n = datasets.open_split(args, sess, split, self.WHO)
+                mean, var = replica.dataset_moments(src, max(1, n // args.batch_size))
+                summaries.write_png(os.path.join(args.dir, 'mean_{}_img.png'.format(name)), np.clip(mean, 0.0, 1.0))
+                summaries.write_png(os.path.join(args.dir, 'var_{}_img.png'.format(name)), np.clip(var, 0.0, 1.0))
+                self.means[split] = mean
+            replica.set_mean_image(self.means['train'])
+
+    def run(self, split, name, title):
+        from tqdm import tqdm
+        summaries = importlib.import_module('3dgan_amd.summaries')
+        replica, args, sess = self.replica, self.args, self.sess
+        src, n_batches = self.sources[split]
+        totals = {}
+        for _ in tqdm(range(n_batches), desc=title, unit='batch'):
+            for k, v in replica.validation_losses(src.next_batch()).items():
+                totals[k] = totals.get(k, 0.0) + float(v)
+        keys = sorted(totals)
+        path = os.path.join(args.dir, 'summaries', name + '.csv')
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        new = not os.path.exists(path)
+        with open(path, 'a') as f:
+            if new:
+                f.write('epoch,step,' + ','.join(keys) + '\n')
+            f.write('%d,%d,' % (sess.global_epoch, sess.global_step) + ','.join('%.8g' % (totals[k] / n_batches) for k in keys) + '\n')
+        if not getattr(args, 'event_files', False):
+            return
+        mean = self.means.get('validate')
+        if mean is not None:
+            replica.set_mean_image(mean)
+        losses = replica.observe(src.next_batch())
+        if split not in self.writers:
+            self.writers[split] = summaries.EventWriter(os.path.join(args.dir, split))
+        replica.write_event(self.writers[split], sess.global_step, losses, montages=getattr(args, 'event_montages', False))
+        if mean is not None:
+            replica.set_mean_image(self.means['train'])
+
+    def close(self):
+        for w in self.writers.values():
+            w.close()
+
+
 def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epochs, saved=None):
     """The epoch / iteration loop and the checkpoint cadence of train.py:279-329, from sess.global_epoch up to max_epochs.
     `saved`: the replica whose state the checkpoints hold (default: `replica`, the one that trains)."""
@@ -138,11 +202,13 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
     status = None
     # --event_files: <dir>/train/events.out.tfevents.*, the reference's summary_writers['train'] (hem/util/training.py:127-158)
     events = summaries.EventWriter(os.path.join(args.dir, 'train')) if chief and getattr(args, 'event_files', False) else None
+    ev_kw = {'montages': True} if getattr(args, 'event_montages', False) else {}                       # --event_montages
+    validation = Validation(replica, args, sess) if chief and getattr(args, 'validation', False) else None
     if sess.global_step == 0 and chief:
         message('Generating baseline checkpoint...')
         ckpt.save(os.path.join(args.dir, 'checkpoint-0.npz'), saved, sess)                             # train.py:288-291
         if events is not None:
-            replica.write_event(events, sess.global_step, {})                                          # training.py:129-130
+            replica.write_event(events, sess.global_step, {}, **ev_kw)                                # training.py:129-130
     if chief:
         message('Starting training...')
     try:
@@ -162,10 +228,10 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
                 if chief:
                     pbar.set_postfix(util.format_for_terminal(dict(status), prev_status))
                 if events is not None and summaries.event_due(epoch, i, iter_per_epoch):               # training.py:142-150
-                    replica.write_event(events, sess.global_step, status)
+                    replica.write_event(events, sess.global_step, status, **ev_kw)
             sess.global_epoch += 1                                                                     # train.py:322
             if events is not None:
-                replica.write_event(events, sess.global_step, status or {})                            # training.py:157-159
+                replica.write_event(events, sess.global_step, status or {}, **ev_kw)                  # training.py:157-159
             if chief:
                 real, fake = replica.samples(args.examples) if hasattr(replica, 'samples') else (None, None)
                 summaries.write_epoch(os.path.join(args.dir, 'summaries'), sess.global_epoch, status or {}, real, fake,
@@ -174,8 +240,14 @@ def run_epochs(train_func, replica, args, sess, chief, iter_per_epoch, max_epoch
                     replica.write_montages(os.path.join(args.dir, 'summaries'), sess.global_epoch)
                 ckpt.save(os.path.join(args.dir, 'checkpoint-{}.npz'.format(sess.global_epoch)), saved, sess)   # :329
                 ckpt.prune(args.dir, getattr(args, 'max_to_keep', 0))                                   # gen-2 --max_to_keep
+            if validation is not None:                                                                 # paper_train.py:101-107
+                validation.run('validate', 'validation', 'Validation')
+                if (epoch + 1) in args.test_epochs:
+                    validation.run('test', 'test', 'Test')
         if events is not None:
             events.close()
+        if validation is not None:
+            validation.close()
     except Exception as e:
         # gen-2's convention (hem/util/training.py:173-175): report and leave with -1, the status repeat.sh restarts on
         # (it resumes from the newest checkpoint in --dir); the library's status text travels in the exception
