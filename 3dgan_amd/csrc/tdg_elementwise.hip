@@ -1808,6 +1808,9 @@ struct Philox {
   }
 };
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }   // [0,1)
+// The *_dev forms start draw d at counter (d + 1) << 24: a window of 2^24 counters, 4 values each.  A longer draw would run
+// into the next draw's counters, so the entry points refuse it.
+static const size_t TDG_DRAW_WINDOW = (size_t)1 << 26;
 
 template <typename T>
 __global__ void __launch_bounds__(256) random_normal_kernel(uint64_t seed, uint64_t sid, uint64_t offset, int* __restrict__ draw_dev,
@@ -1846,6 +1849,8 @@ extern "C" int tdg_random_normal(int dtype, uint64_t seed, uint64_t stream_id, u
 extern "C" int tdg_random_normal_dev(int dtype, uint64_t seed, uint64_t stream_id, int32_t* draw_dev, size_t n, void* out,
                                      void* stream) {
   TDG_CHECK_ARG(out && draw_dev && n > 0, "tdg_random_normal_dev: bad argument");
+  TDG_CHECK_ARG(n <= TDG_DRAW_WINDOW, "tdg_random_normal_dev: n = %zu exceeds the draw's window of 2^24 counters = %zu values "
+                "(the draw would run into the next draw's counters)", n, TDG_DRAW_WINDOW);
   TDG_TICKET_STREAM("tdg_random_normal_dev", stream);
   DISPATCH_T(dtype, {
     hipLaunchKernelGGL(random_normal_kernel<T>, dim3(ew_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, seed,
@@ -1878,6 +1883,8 @@ extern "C" int tdg_random_uniform_f32(uint64_t seed, uint64_t stream_id, uint64_
 extern "C" int tdg_random_uniform_f32_dev(uint64_t seed, uint64_t stream_id, int32_t* draw_dev, size_t n, float* out,
                                           void* stream) {
   TDG_CHECK_ARG(out && draw_dev && n > 0, "tdg_random_uniform_f32_dev: bad argument");
+  TDG_CHECK_ARG(n <= TDG_DRAW_WINDOW, "tdg_random_uniform_f32_dev: n = %zu exceeds the draw's window of 2^24 counters = %zu values "
+                "(the draw would run into the next draw's counters)", n, TDG_DRAW_WINDOW);
   TDG_TICKET_STREAM("tdg_random_uniform_f32_dev", stream);
   hipLaunchKernelGGL(random_uniform_kernel, dim3(ew_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, seed,
                      stream_id, (uint64_t)0, draw_dev, n, out);

@@ -623,9 +623,12 @@ int tdg_random_uniform_f32(uint64_t seed, uint64_t stream_id, uint64_t offset, s
                            void* stream);
 /* Graph-replayable forms: the counter offset is ((draw_dev[0] + 1) << 24), read from device memory, and the kernel
  * itself counts the draw (draw_dev[0] += 1, by its last block), so a replay of the same launch is a fresh draw.
- * ONE-STREAM RULE: the kernel hands its last block a ticket from a per-process device-global slot, so launches of this entry point must not overlap on the device; the library returns TDG_EINVAL if it is launched on a second (non-capturing) stream of the process. */
+ * ONE-STREAM RULE: the kernel hands its last block a ticket from a per-process device-global slot, so launches of this entry point must not overlap on the device; the library returns TDG_EINVAL if it is launched on a second (non-capturing) stream of the process.
+ * DRAW WINDOW: each draw owns 2^24 counters, i.e. 2^26 values; n > 2^26 would run into the next draw's counters and
+ * returns TDG_EINVAL (n == 2^26 is legal). */
 int tdg_random_normal_dev(int dtype, uint64_t seed, uint64_t stream_id, int32_t* draw_dev, size_t n,
                           void* out, void* stream);
+/* (the same window: n > 2^26 returns TDG_EINVAL) */
 int tdg_random_uniform_f32_dev(uint64_t seed, uint64_t stream_id, int32_t* draw_dev, size_t n, float* out,
                                void* stream);
 
