@@ -288,10 +288,20 @@ extern "C" int tdg_cgan_prep(int dtype, const float* y, int n, int version, void
     default: tdg_set_error("tdg_cgan_head: cin %d is not 64, 128, 256 or 512", (cin)); return TDG_EINVAL; \
   }
 
+// What the two dispatches below would reject, rejected with the other argument checks: before the timing window opens, so
+// that a refused head call records nothing -- and with cin compared as a whole (cin / 8 let 65 .. 71 pass as 64).
+#define CGAN_HEAD_CHECK(what, dtype, cin)                                                                               \
+  do {                                                                                                                  \
+    TDG_CHECK_ARG((dtype) == TDG_BF16 || (dtype) == TDG_F32, "%s: bad dtype %d", (what), (int)(dtype));                 \
+    TDG_CHECK_ARG((cin) == 64 || (cin) == 128 || (cin) == 256 || (cin) == 512, "%s: cin %d is not 64, 128, 256 or 512", \
+                  (what), (int)(cin));                                                                                  \
+  } while (0)
+
 // both head forwards: u == nullptr is the cin -> 1 head, else the cin + 1 -> 1 head of --noise_layer d4
 static int head_fwd(const char* what, int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w,
                     const float* b, const float* u, const float* ybar, float* yhat, float* g32, void* fake, int fake_cs,
                     hipStream_t stream) {
+  CGAN_HEAD_CHECK(what, dtype, cin);
   tdg_timing_start(what, 0.0, stream);
   DISPATCH_T(dtype, {
     CGAN_TPP_DISPATCH(cin, {
@@ -311,6 +321,7 @@ static int head_fwd(const char* what, int dtype, const void* cat, int n, int hw,
 static int head_bwd(const char* what, int dtype, const void* dfake, int fake_cs, const void* cat, int n, int hw, int cin, int cs,
                     int crop, const float* w, const float* u, int mask_mode, float leak, void* dcat, float* dw, float* db,
                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  CGAN_HEAD_CHECK(what, dtype, cin);
   const int cols = cin + (u ? 2 : 1);
   if (workspace_bytes < (size_t)n * cols * sizeof(float)) {
     tdg_set_error("%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, (size_t)n * cols * sizeof(float));

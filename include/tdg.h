@@ -287,7 +287,8 @@ int tdg_cgan_prep(int dtype, const float* y, int n, int version, void* depth_rea
                   float* crop, void* g_ones, int g_cs, void* rgb_ybar, int rgb_cs, void* stream);
 /* tdg_cgan_head_fwd: the generator head d4 (1x1 conv, cin -> 1, no activation) on the top-left crop x crop pixels of the
  * hw x hw concat [n,hw,hw,cs] only (:241-242): g = w . cat + b.  yhat = g + ybar[b] (ybar nullable: + 0), f32 [n,crop,crop];
- * fake (channel 0 of D's fake depth input, channel stride fake_cs, compute dtype) = g.  cin in {64,128,256,512}. */
+ * fake (channel 0 of D's fake depth input, channel stride fake_cs, compute dtype) = g.  cin in {64,128,256,512}: any other
+ * cin, like a bad dtype, is TDG_EINVAL for all four head entries, before anything is launched or timed. */
 int tdg_cgan_head_fwd(int dtype, const void* cat, int n, int hw, int cin, int cs, int crop, const float* w, const float* b,
                       const float* ybar, float* yhat, void* fake, int fake_cs, void* stream);
 /* tdg_cgan_head_bwd: from delta = dL/dg (channel 0 of dfake, [n,crop,crop,fake_cs]):

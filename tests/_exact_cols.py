@@ -588,3 +588,186 @@ def restate_rowdot(x, w, bias, defect=None):
     """rowdot_kernel.  Defect 'drop_last_col': the column loop stops one short."""
     n = x.shape[1] - (1 if defect == 'drop_last_col' else 0)
     return ((x[:, :n] * w[None, :n]).astype(np.float32).sum(1, dtype=np.float32) + bias[0]).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ instance norm
+# tdg_instance_norm_fwd / _bwd: the one normalisation that reduces in f32 for both dtypes.  Per (image, channel):
+#   d = u - u[0],  md = fl(s0 / hw),  var = max(fl(fl(s1 / hw) - fl(md md)), 0),  mu = fl(u[0] + md),  rstd = rsqrtf(fl(var + eps)).
+# The tables keep s0 and s1 exact (integers below 2**24, asserted on the CPU); everything behind them goes through the Ev
+# algebra of tests/_exact_pointwise.py (imported inside the functions: that module imports this one).
+IN_CASES = [(1, 1, 1), (2, 4, 64), (3, 5, 65), (2, 64, 63), (1, 4100, 3), (2, 16, 130)]         # (n, hw, c)
+IN_ACTS = (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH)
+IN_OUTLIER = 200.0
+IN_SCALES = (0.5, 1.0, 2.0, -1.0, 1.5, -0.5)
+IN_SHIFTS = (0.25, -0.25, 0.5, -0.5, 0.75, -0.75, 1.0, -1.0)          # never 0: a constant column's pre is its shift
+
+
+def in_id(k):
+    return 'n%d-hw%d-c%d' % tuple(k)
+
+
+def in_strides(c):
+    """(cs, h_cs, dh_cs): all above c, all different."""
+    return c + 3, c + 1, c + 6
+
+
+def in_outlier_column(c):
+    return c - 2 if c >= 6 else None
+
+
+def in_sum_depth(hw):
+    """A row lane's serial run (every fourth position), then sh[0] + sh[1] + sh[2] + sh[3]."""
+    return -(-hw // 4) + 3
+
+
+def in_inputs(k, tag=50):
+    """u[b, :, j] = BASES[j % 5] + integers in [-3, 3]; the last column constant (c >= 6: the variance is 0 and rstd comes from
+    eps alone), the one before it integers in [-3, 3] whose FIRST position is +-200 (the pivot is the outlier and does not
+    help); scale from IN_SCALES, shift from IN_SHIFTS, dh and the dscale / dshift prefills eighths in [-1, 1]."""
+    n, hw, c = k
+    rng = _rng(k, tag)
+    base = np.array([BASES[j % 5] for j in range(c)], dtype=np.float32)
+    u = base[None, None, :] + _ints(rng, -3, 3, (n, hw, c))
+    if const_column(c) is not None:
+        u[:, :, const_column(c)] = base[const_column(c)]
+        oc = in_outlier_column(c)
+        u[:, :, oc] = _ints(rng, -3, 3, (n, hw))
+        u[:, 0, oc] = IN_OUTLIER * np.where(np.arange(n) % 2 == 0, 1, -1)
+    pick = lambda pool: np.asarray(pool, dtype=np.float32)[rng.integers(0, len(pool), c)]          # noqa: E731
+    return NS(u=u, scale=pick(IN_SCALES), shift=pick(IN_SHIFTS), dh=_ints(rng, -8, 8, (n, hw, c)) / np.float32(8),
+              old_dscale=_ints(rng, -8, 8, c) / np.float32(8), old_dshift=_ints(rng, -8, 8, c) / np.float32(8))
+
+
+def in_stats_ref(u):
+    """float64 moments per (image, channel) as deviations from the image's first position (exact: integers)."""
+    u = u.astype(np.float64)
+    d = u - u[:, :1]
+    hw = u.shape[1]
+    s0, s1 = d.sum(1), (d * d).sum(1)
+    md = s0 / hw
+    return NS(s0=s0, s1=s1, hw=hw, pivot=u[:, 0], md=md, e2=s1 / hw, mean=u[:, 0] + md, var=s1 / hw - md * md,
+              abs0=np.abs(d).sum(1))
+
+
+def in_caps(inp):
+    st = in_stats_ref(inp.u)
+    check_caps(inp.u, 'bf16', 'u')
+    check_caps(st.abs0, 'f32', 'sum |d|')
+    check_caps(st.s1, 'f32', 'sum d^2')
+    for v in (inp.u, inp.scale, inp.shift, inp.dh, inp.old_dscale, inp.old_dshift):
+        assert np.array_equal(bf16_round(v), v)
+
+
+def in_mu_ref(st):
+    """(mu, bound): fl(pivot + fl(s0 / hw)) from the exact s0."""
+    from _exact_pointwise import Ev, add, div
+    mu = add(Ev(st.pivot), div(Ev(st.s0), float(st.hw)))
+    return mu.v, mu.e
+
+
+def in_rstd_interval(st, eps):
+    """rstd_interval restated for the f32 path: var through two divisions, a product and a subtraction (Ev), the clamp (it
+    moves the device's variance towards the true one, which is >= 0, and leaves fl(var + eps) >= eps), one addition and
+    rsqrtf at RSQRT_ULP.  rsqrt falls with its argument.  Returns (rstd, lo, hi, amplification)."""
+    from _exact_pointwise import Ev, add, sub, mul, div, RSQRT_ULP, ULP, f32c
+    md, e2 = div(Ev(st.s0), float(st.hw)), div(Ev(st.s1), float(st.hw))
+    var = sub(e2, mul(md, md))
+    e = f32c(eps)
+    arg = add(Ev(np.maximum(var.v, 0.0), var.e), e)
+    rstd = 1.0 / np.sqrt(arg.v)
+    lo = (1.0 - RSQRT_ULP * ULP) / np.sqrt(arg.v + arg.e)
+    hi = (1.0 + RSQRT_ULP * ULP) / np.sqrt(np.maximum(arg.v - arg.e, e))
+    return rstd, lo, hi, (st.e2 + st.md * st.md) / np.maximum(st.var, e)
+
+
+def _in_pre(inp, mu, rstd):
+    """xhat = fl(fl(u - mu) rstd) and the backward's pre = fl(fl(scale xhat) + shift) at the given f32 statistics."""
+    from _exact_pointwise import Ev, add, sub, mul
+    xh = mul(sub(Ev(inp.u), Ev(np.asarray(mu, np.float64)[:, None, :])), Ev(np.asarray(rstd, np.float64)[:, None, :]))
+    return xh, add(mul(Ev(inp.scale), xh), Ev(inp.shift))
+
+
+def in_apply_ref(inp, mu, rstd, act, dtype):
+    """h = act(fl(fl(fl(scale fl(u - mu)) rstd) + shift)) in float64 at the DEVICE's statistics (read back), as bn_apply_ref
+    does: (reference, bound).  none / relu / lrelu (leak 0.25: an exact product) are 1-Lipschitz and round nothing."""
+    from _exact_pointwise import Ev, add, sub, mul, ev_tanh, stored
+    x = sub(Ev(inp.u), Ev(np.asarray(mu, np.float64)[:, None, :]))
+    pre = add(mul(mul(Ev(inp.scale), x), Ev(np.asarray(rstd, np.float64)[:, None, :])), Ev(inp.shift))
+    h = ev_tanh(pre) if act == ACT_TANH else type(pre)(act_ref(pre.v, act), pre.e)
+    return stored(h, dtype)
+
+
+def _ev_sum(t, axis, depth):
+    from _exact_pointwise import Ev, TINY
+    return Ev(t.v.sum(axis), t.e.sum(axis) + gamma(depth, U32) * (np.abs(t.v) + t.e).sum(axis) + TINY)
+
+
+def in_bwd_ref(inp, mu, rstd, act, dtype, beta):
+    """Every output of tdg_instance_norm_bwd at the given statistics: du [n, hw, c] (reference, bound), dscale and dshift [c]
+    (reference, bound; beta * old added), and `kink`: min(|pre| - its bound) over the tensor, which must be positive for
+    relu / lrelu -- their derivative is read off the sign of pre.  g = dh act'(pre); s0 = sum g, s1 = sum g xhat per image
+    through the kernel's tree (in_sum_depth); du = fl(scale rstd) * ((g - s0 / hw) - xhat * (s1 / hw)); the images' partials
+    meet in the finalize kernel: n additions, the prefill's, one cast."""
+    from _exact_pointwise import Ev, sub, mul, div, ev_tanh, stored
+    n, hw, c = inp.u.shape
+    xh, pre = _in_pre(inp, mu, rstd)
+    if act == ACT_TANH:
+        t = ev_tanh(pre)
+        f = sub(1.0, mul(t, t))
+    else:
+        f = Ev(act_deriv_ref(pre.v, act))
+    g = mul(Ev(inp.dh), f)
+    t1 = mul(g, xh)
+    s0, s1 = _ev_sum(g, 1, in_sum_depth(hw)), _ev_sum(t1, 1, in_sum_depth(hw))
+    wide = lambda s: Ev(s.v[:, None, :], s.e[:, None, :])                                            # noqa: E731
+    m0, m1 = wide(div(s0, float(hw))), wide(div(s1, float(hw)))
+    du = mul(mul(Ev(inp.scale), Ev(np.asarray(rstd, np.float64)[:, None, :])), sub(sub(g, m0), mul(xh, m1)))
+    out = NS(kink=float((np.abs(pre.v) - pre.e).min()), g=g.v, s0=s0.v)
+    out.du, out.du_bound = stored(du, dtype)
+    for name, s, old in (('dscale', s1, inp.old_dscale), ('dshift', s0, inp.old_dshift)):
+        o = beta * old.astype(np.float64)
+        setattr(out, name, s.v.sum(0) + o)
+        setattr(out, name + '_bound', s.e.sum(0) + gamma(n + 2, U32) * ((np.abs(s.v) + s.e).sum(0) + np.abs(o)))
+    return out
+
+
+def in_kink_margin(inp, eps):
+    """The kink condition without a device: min over the tensor of |pre| - (its rounding bound + what the intervals of mu and
+    rstd can move it by), pre at the float64 statistics."""
+    st = in_stats_ref(inp.u)
+    mu, e_mu = in_mu_ref(st)
+    rstd, lo, hi, _ = in_rstd_interval(st, eps)
+    _, pre = _in_pre(inp, mu, rstd)
+    d_rstd = np.maximum(hi - rstd, rstd - lo)
+    x = np.abs(inp.u.astype(np.float64) - mu[:, None, :])
+    moved = np.abs(inp.scale.astype(np.float64)) * (x * d_rstd[:, None, :] + e_mu[:, None, :] * (rstd + d_rstd)[:, None, :])
+    return float((np.abs(pre.v) - pre.e - moved * (1 + 2.0 ** -20)).min())
+
+
+def restate_in_stats(u, eps, defect=None, sums=None):
+    """instance_norm_fwd_kernel's statistics in f32: (mu, rstd) [n, c].  Defects: 'no_pivot' (raw moments), 'no_clamp' (the
+    variance is not clamped at 0).  sums: (s0, s1, hw, pivot) in place of a tensor."""
+    f = np.float32
+    if sums is None:
+        pivot = np.zeros_like(u[:, 0]) if defect == 'no_pivot' else u[:, 0]
+        d = (u - pivot[:, None]).astype(f)
+        s0, s1, hw = d.sum(1, dtype=f), (d * d).astype(f).sum(1, dtype=f), u.shape[1]
+    else:
+        s0, s1, hw, pivot = (np.asarray(sums[0], f), np.asarray(sums[1], f), sums[2], np.asarray(sums[3], f))
+    md = (s0 / f(hw)).astype(f)
+    var = ((s1 / f(hw)).astype(f) - (md * md).astype(f)).astype(f)
+    if defect != 'no_clamp':
+        var = np.maximum(var, f(0))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        rstd = (f(1) / np.sqrt((var + f(eps)).astype(f))).astype(f)
+    return (pivot + md).astype(f), rstd
+
+
+def restate_in_bwd_sums(inp, mu, rstd, act, defect=None):
+    """(dscale, dshift) of instance_norm_bwd_kernel in f32 at beta = 0.  Defect 'swapped': each lands in the other's vector."""
+    f = np.float32
+    xh = ((inp.u - mu[:, None, :]).astype(f) * rstd[:, None, :]).astype(f)
+    pre = ((inp.scale * xh).astype(f) + inp.shift).astype(f)
+    g = (inp.dh * act_deriv_ref(pre.astype(np.float64), act).astype(f)).astype(f)
+    dshift, dscale = g.sum((0, 1), dtype=f), (g * xh).astype(f).sum((0, 1), dtype=f)
+    return (dshift, dscale) if defect == 'swapped' else (dscale, dshift)

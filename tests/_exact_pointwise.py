@@ -39,6 +39,7 @@ LOG1P_ULP = 2
 POW_ULP = 16
 SQRT_ULP = 3
 DIV_ULP = 2.5
+RSQRT_ULP = 2                     # rsqrt in the same table (section 7.4, full profile, single precision): <= 2 ulp
 ULP = 2.0 ** -23                  # ulp(x) <= 2**-23 |x|
 TINY = 2.0 ** -126                # the smallest normal f32: results below it may be flushed
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4      # include/tdg.h (the host test ties them to _lib)
@@ -130,6 +131,11 @@ def ev_tanh(a):
 
 def ev_sqrt(a):
     return mono(a, lambda x: np.sqrt(np.maximum(x, 0.0)), SQRT_ULP)
+
+
+def ev_rsqrt(a):
+    """rsqrtf of a positive argument (monotone decreasing)."""
+    return mono(a, lambda x: 1.0 / np.sqrt(np.maximum(x, 0.0)), RSQRT_ULP)
 
 
 def ev_pow(base, t):

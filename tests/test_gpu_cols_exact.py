@@ -507,3 +507,83 @@ def test_rowdot_and_rowouter(shape, off, dtype):
         call('tdg_rowouter', dtype, K().ptr(dout), K().ptr(w), rows, cols, mode, X.LEAK, mask.ptr() if masked else None, dx.ptr(), K().stream())
         exact(dx.get(), X.store(X.rowouter_ref(inp, masked), dtype), 'rowouter %dx%d off=%d masked=%s' % (rows, cols, off, masked))
     x.get(), mask.get()
+
+
+# ------------------------------------------------------------------------------------------------ 8. instance norm
+IN_CASE_ACTS = [(k, a) for k in X.IN_CASES for a in X.IN_ACTS]
+IN_CASE_ACT_IDS = ['%s-%s' % (X.in_id(k), ACT_NAME[a]) for k, a in IN_CASE_ACTS]
+RSQRT_ULP = 2                                           # tests/_exact_pointwise.py (OpenCL 1.2 full profile)
+
+
+@functools.lru_cache(maxsize=2)
+def in_inputs(k):
+    inp = X.in_inputs(k)
+    inp.st = X.in_stats_ref(inp.u)
+    return inp
+
+
+def run_instance_norm(k, dtype, act, beta):
+    """tdg_instance_norm_fwd, then tdg_instance_norm_bwd on the statistics it left.  cs, h_cs and dh_cs all differ and lie
+    above c: u and dh are NaN in their padding channels, h and du keep the sentinel there; scale, shift, stats and the
+    workspace are followed by guards."""
+    n, hw, c = k
+    inp = in_inputs(k)
+    cs, h_cs, dh_cs = X.in_strides(c)
+    rows = n * hw
+    u, dh = Buf(X.Layout(rows, c, cs), dtype, inp.u.reshape(rows, c)), Buf(X.Layout(rows, c, dh_cs), dtype, inp.dh.reshape(rows, c))
+    h, du = Buf(X.Layout(rows, c, h_cs), dtype), Buf(X.Layout(rows, c, cs), dtype)
+    scale, shift = (torch.from_numpy(np.concatenate([v, nans(8)])).to(dev()) for v in (inp.scale, inp.shift))
+    stats, ws = fvec(nans(n * 2 * c)), fvec(nans(n * 2 * c))
+    call('tdg_instance_norm_fwd', dtype, u.ptr(), n, hw, c, cs, K().ptr(scale), K().ptr(shift), X.EPS, act, X.LEAK, h.ptr(), h_cs,
+         K().ptr(stats), K().stream())
+    dscale, dshift = fvec(inp.old_dscale if beta else nans(c)), fvec(inp.old_dshift if beta else nans(c))
+    call('tdg_instance_norm_bwd', dtype, dh.ptr(), dh_cs, u.ptr(), n, hw, c, cs, K().ptr(scale), K().ptr(shift), K().ptr(stats), act,
+         X.LEAK, du.ptr(), K().ptr(dscale), K().ptr(dshift), beta, K().ptr(ws), n * 2 * c * 4, K().stream())
+    st = vget(stats, n * 2 * c).reshape(n, 2, c)
+    vget(ws, n * 2 * c), u.get(), dh.get()
+    return dict(mu=st[:, 0].copy(), rstd=st[:, 1].copy(), h=h.get().reshape(n, hw, c), du=du.get().reshape(n, hw, c),
+                dscale=vget(dscale, c), dshift=vget(dshift, c))
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('k,act', IN_CASE_ACTS, ids=IN_CASE_ACT_IDS)
+def test_instance_norm(k, act, dtype):
+    """Statistics against float64 moments (mu exact at power-of-two hw, rstd in its f32-path interval, a constant column at
+    1 / sqrt(eps), a column whose pivot is a +-200 outlier), then h, du and dscale per element against the float64 formulas at
+    the device's own statistics and dshift exactly (none / relu / lrelu on eighths), with beta 0 and 1; no pre of the table
+    lies within its bound of the relu / lrelu kink; two launches are bit-equal."""
+    n, hw, c = k
+    inp = in_inputs(k)
+    what = '%s instance_norm %s %s' % (DT[dtype], X.in_id(k), ACT_NAME[act])
+    a, b = run_instance_norm(k, dtype, act, 0.0), run_instance_norm(k, dtype, act, 0.0)
+    for name in a:
+        assert np.array_equal(a[name].view(np.uint32), b[name].view(np.uint32)), '%s: %s differs between two launches' % (what, name)
+    mu, rstd = a['mu'], a['rstd']
+    if hw & (hw - 1) == 0:
+        exact(mu, inp.st.mean, what + ' mu')
+    else:
+        within(X.bound_ratio(mu, *X.in_mu_ref(inp.st)), what + ' mu')
+    want, lo, hi, amp = X.in_rstd_interval(inp.st, X.EPS)
+    within(X.interval_ratio(rstd, want, lo, hi), what + ' rstd (amplification up to %.3g)' % amp.max())
+    const = X.const_column(c)
+    if const is not None:
+        assert np.all(inp.st.var[:, const] == 0) and np.all(X.ulps(rstd[:, const], RSTD_CLAMPED) <= RSQRT_ULP), rstd[:, const]
+        assert np.all(np.abs(inp.u[:, 0, X.in_outlier_column(c)]) == X.IN_OUTLIER)
+    within(X.bound_ratio(a['h'], *X.in_apply_ref(inp, mu, rstd, act, dtype)), what + ' h')
+    ref = X.in_bwd_ref(inp, mu, rstd, act, dtype, 0.0)
+    if act in (X.ACT_RELU, X.ACT_LRELU):
+        assert ref.kink > 0, '%s: an element of pre lies within its bound of 0 (margin %g)' % (what, ref.kink)
+    if hw == 1:
+        exact(a['du'], np.zeros((n, hw, c)), what + ' du at hw 1')
+        if act != X.ACT_TANH:
+            exact(a['h'], np.broadcast_to(X.store(X.act_ref(inp.shift.astype(np.float64), act), dtype), (n, hw, c)), what + ' h == act(shift)')
+    c1 = run_instance_norm(k, dtype, act, 1.0)
+    exact(c1['du'], a['du'], what + ': du, beta = 1')
+    ref1 = X.in_bwd_ref(inp, mu, rstd, act, dtype, 1.0)
+    for r, got, beta in ((ref, a, 0), (ref1, c1, 1)):
+        within(X.bound_ratio(got['du'], r.du, r.du_bound), what + ' du')
+        within(X.bound_ratio(got['dscale'], r.dscale, r.dscale_bound), what + ' dscale, beta = %d' % beta)
+        if act == X.ACT_TANH:
+            within(X.bound_ratio(got['dshift'], r.dshift, r.dshift_bound), what + ' dshift, beta = %d' % beta)
+        else:
+            exact(got['dshift'], r.dshift, what + ' dshift, beta = %d' % beta)

@@ -214,3 +214,90 @@ def test_restated_scalar_and_row_reductions_with_defects():
     inp = X.row_inputs(3, 1028)
     assert np.array_equal(X.restate_rowdot(inp.x, inp.w, inp.bias), X.rowdot_ref(inp))
     assert not np.array_equal(X.restate_rowdot(inp.x, inp.w, inp.bias, 'drop_last_col'), X.rowdot_ref(inp))
+
+
+# ------------------------------------------------------------------------------------------------ instance norm
+IN_IDS = [X.in_id(k) for k in X.IN_CASES]
+
+
+def test_instance_norm_constants():
+    import _exact_pointwise as P
+    # OpenCL 1.2 section 7.4, full profile, single precision: rsqrt <= 2 ulp, beside the limits already taken from that table
+    assert (P.RSQRT_ULP, P.SQRT_ULP, P.DIV_ULP) == (2, 3, 2.5)
+    r = P.ev_rsqrt(P.Ev(np.array([4.0]), np.array([0.0])))
+    assert r.v[0] == 0.5 and 0 < r.e[0] <= 2.0 ** -23
+
+
+@pytest.mark.parametrize('k', X.IN_CASES, ids=IN_IDS)
+def test_instance_norm_table_conditions(k):
+    """The sums the bounds take as exact are exact (integers below 2**24), mu is representable at power-of-two hw, the
+    constant column has variance 0, the outlier column's pivot is +-200, strides lie above c -- and the kink condition:
+    in float64, with everything the statistics' own intervals can move, no pre of any case lies within its bound of 0."""
+    n, hw, c = k
+    inp = X.in_inputs(k)
+    X.in_caps(inp)
+    st = X.in_stats_ref(inp.u)
+    assert np.array_equal(st.s0, np.rint(st.s0)) and np.array_equal(st.s1, np.rint(st.s1))
+    if hw & (hw - 1) == 0:
+        assert X.fits_f32(st.mean) and X.fits_f32(st.md) and np.all(X.in_mu_ref(st)[0] == st.mean)
+    if X.const_column(c) is not None:
+        assert np.all(st.var[:, X.const_column(c)] == 0) and np.all(np.abs(inp.u[:, 0, X.in_outlier_column(c)]) == X.IN_OUTLIER)
+        assert np.all(st.var[:, X.in_outlier_column(c)] > 100)
+    assert min(X.in_strides(c)) > c and len(set(X.in_strides(c))) == 3
+    assert np.all(inp.shift != 0) and np.all(inp.scale != 0)
+    margin = X.in_kink_margin(inp, X.EPS)
+    assert margin > 0, margin
+    if hw == 1:
+        assert np.all(st.var == 0) and np.all(st.mean == inp.u[:, 0])
+    a, b = vars(X.in_inputs(k)), vars(X.in_inputs(k))
+    assert all(np.array_equal(a[name], b[name]) for name in a)
+
+
+@pytest.mark.parametrize('k', X.IN_CASES, ids=IN_IDS)
+def test_instance_norm_restated_clean_and_with_defects(k):
+    """The f32 restatement of the statistics holds the mu bound and the rstd interval on every column, the outlier column
+    included (there the pivot is the outlier: every deviation is ~200 and the amplification is the table's largest).
+    Without the pivot it is the columns that sit at +-200 whose rstd leaves the interval (at hw 5 and 64; at hw 4 and 16 every
+    intermediate of the raw moments is still representable); the outlier column alone is not hurt by raw moments, since
+    all its other values are small.  dscale and dshift swapped are rejected.  The unclamped
+    variance cannot be exposed by a tensor: with exact sums a column's f32 variance is negative only if its true variance
+    is below a rounding of its second moment, and deviations from the column's own first value cannot have that shape
+    (a constant column gives 0 - 0) -- so that defect is rejected on hand-made sums (md = 2, E[d^2] = 1)."""
+    n, hw, c = k
+    inp = X.in_inputs(k)
+    st = X.in_stats_ref(inp.u)
+    want, lo, hi, amp = X.in_rstd_interval(st, X.EPS)
+    muv, mue = X.in_mu_ref(st)
+    mu, rstd = X.restate_in_stats(inp.u, X.EPS)
+    assert X.bound_ratio(mu, muv, mue).max() <= 1 and X.interval_ratio(rstd, want, lo, hi).max() <= 1
+    same, _ = X.restate_in_stats(inp.u, X.EPS, 'no_clamp')
+    assert np.array_equal(same, mu)
+    if c >= 6 and hw > 1:
+        assert amp[:, X.in_outlier_column(c)].min() == amp.max() or amp[:, X.in_outlier_column(c)].min() > 0.5 * amp.max()
+        _, bad = X.restate_in_stats(inp.u, X.EPS, 'no_pivot')
+        r = X.interval_ratio(bad, want, lo, hi)
+        far = np.array([abs(X.BASES[j % 5]) == 200 and j not in (X.const_column(c), X.in_outlier_column(c)) for j in range(c)])
+        if hw & (hw - 1) or hw >= 64:
+            assert far.any() and np.mean(r[:, far] > 1) > 0.5 and r[:, far].max() > 100, (np.mean(r[:, far] > 1), r[:, far].max())
+        else:                                           # hw 4 and 16 on integers: s / hw and md * md are exact, raw moments lose nothing
+            assert far.any() and r.max() <= 1
+    for act in (X.ACT_NONE, X.ACT_RELU, X.ACT_LRELU, X.ACT_TANH):
+        ref = X.in_bwd_ref(inp, mu, rstd, act, 1, 0.0)
+        accepts = lambda ds, dsh: (X.bound_ratio(ds, ref.dscale, ref.dscale_bound).max() <= 1 and                    # noqa: E731
+                                   (X.bound_ratio(dsh, ref.dshift, ref.dshift_bound).max() <= 1 if act == X.ACT_TANH
+                                    else np.array_equal(dsh, ref.dshift)))
+        assert accepts(*X.restate_in_bwd_sums(inp, mu, rstd, act)), act
+        if hw > 1:
+            assert not accepts(*X.restate_in_bwd_sums(inp, mu, rstd, act, 'swapped')), act
+        hv, hb = X.in_apply_ref(inp, mu, rstd, act, 0)
+        assert np.all(np.isfinite(hv)) and np.all(hb >= 0) and (act not in (X.ACT_RELU, X.ACT_LRELU) or ref.kink > 0)
+
+
+def test_instance_norm_unclamped_variance_is_rejected_on_hand_made_sums():
+    hw = 64
+    sums = (np.array([[2.0 * hw]]), np.array([[1.0 * hw]]), hw, np.array([[0.0]]))
+    want = 1 / np.sqrt(np.float64(np.float32(X.EPS)))
+    _, rstd = X.restate_in_stats(None, X.EPS, sums=sums)
+    assert X.ulps(rstd[0, 0], want) <= 2
+    _, rstd = X.restate_in_stats(None, X.EPS, 'no_clamp', sums=sums)
+    assert not X.ulps(rstd[0, 0], want) <= 2
